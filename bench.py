@@ -20,7 +20,11 @@ exact (the dense backward multiplies zeros), counted as what it aggregates.
     value = edges_per_s = num_layers * E_msg / step_s      (BASELINE.md §2 definition)
     edges_aggregated_per_step = nonzeros actually aggregated, forward + backward
 
-Secondary measurements in the same JSON line (unless --no-extra):
+A plain run sets up, warms up, times --steps steps, writes the last step's outputs if
+--dump-outputs DIR is given, and prints the result line.
+
+Secondary measurements in the same JSON line, with --full only (the first three unless
+--no-extra):
   * "structureless": the same step on a --global-frac 1.0 graph (uniformly random
     endpoints: no locality for any cache to exploit);
   * "bf16_stack": the headline graph at bf16 storage/compute on the layer-stack path
@@ -88,7 +92,8 @@ def parse():
                     help="headline = train-rows-only step (output layer aggregated at the "
                          "train rows only); NOT a full-graph step, for A/B only")
     ap.add_argument("--no-extra", action="store_true",
-                    help="skip the structureless-graph and train-rows-only measurements")
+                    help="with --full: skip the structureless-graph, bf16 and train-rows-only "
+                         "measurements")
     ap.add_argument("--extra-steps", type=int, default=3)
     ap.add_argument("--verbose", action="store_true")
     ap.add_argument("--rehearse-world", type=int, default=0,
@@ -127,6 +132,19 @@ def parse():
                     default=float(os.environ.get("DGRAPH_BENCH_SHMEM_PROBE_TIMEOUT_S", "150")))
     ap.add_argument("--metrics-jsonl", default=os.environ.get("DGRAPH_METRICS_JSONL", ""),
                     help="append one metrics record per measured phase (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run everything else this benchmark "
+                         "measures: the per-region breakdown (one extra step), the secondary "
+                         "jobs (structureless graph, bf16 layer stack, train-rows-only; see "
+                         "--no-extra) and, at W > 1, the link probe and the one-sided "
+                         "transport probe. Off by default: a plain run sets up, warms up, "
+                         "times --steps steps and prints the result line (a rehearsal, "
+                         "--rehearse-world, always records its regions)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, rank 0 writes what the last timed step "
+                         "returned and left behind as DIR/<name>.npy: the loss and the "
+                         "validation/test hit counts (float64), every parameter after its "
+                         "Adam update and, where the step keeps them, the gradients (float32)")
     return ap.parse_args()
 
 
@@ -443,6 +461,28 @@ def timed(job: Job, steps: int, warmup: int, restrict_last: bool, verbose: bool 
     return float(red.item()), float(tot[0].item()), float(tot[1].item())
 
 
+def dump_outputs(job: "Job", out_dir: str, loss: float, correct: torch.Tensor) -> None:
+    """What the last timed step handed its caller, as ``out_dir/<name>.npy`` (rank 0): the
+    loss (summed over ranks, as in the result line) and the validation/test hit counts of
+    its forward (float64), every parameter after its Adam update and the gradients the
+    step left in ``p.grad`` (float32; replicated on every rank). A few MB at the default
+    model. The graph, data and initial weights are functions of ``--seed`` alone, so two
+    builds run with the same arguments are comparable file by file."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss.npy"), np.asarray([loss], dtype=np.float64))
+    np.save(os.path.join(out_dir, "correct_val_test.npy"),
+            correct.detach().cpu().numpy().astype(np.float64))
+    for i, (name, p) in enumerate(job.model.named_parameters()):
+        stem = f"{i:02d}_{name.replace('.', '_')}"
+        np.save(os.path.join(out_dir, f"param_{stem}.npy"),
+                p.detach().float().cpu().numpy())
+        if p.grad is not None:
+            np.save(os.path.join(out_dir, f"grad_{stem}.npy"),
+                    p.grad.detach().float().cpu().numpy())
+
+
 def link_probe(job: "Job", width: int = 64, iters: int = 5) -> dict:
     """Achieved xGMI bandwidth of this job's own halo exchange (W > 1, every rank, after
     the timed steps): the plan's all-to-all-v of ``width`` fp32 columns, ``iters`` times
@@ -746,11 +786,15 @@ def main():
         dist.all_reduce(corr)
     val_acc = float(corr[0]) / max(job.n_val, 1)
     test_acc = float(corr[1]) / max(job.n_test, 1)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(job, args.dump_outputs, final_loss, corr)
     halo = job.halo_stats()
     alloc_timed = dict(getattr(job, "alloc_timed", {}))
     mem_setup = getattr(job, "mem_setup_gb", 0.0)
-    regions = region_breakdown(job)
-    xgmi = link_probe(job) if (world > 1 and not job.rehearse) else {}
+    # everything below the headline is --full's (a rehearsal is its own record: one
+    # rank's regions are what it is run for)
+    regions = region_breakdown(job) if (args.full or job.rehearse) else {}
+    xgmi = link_probe(job) if (args.full and world > 1 and not job.rehearse) else {}
     use_fused = job.use_fused
     schedule = job.fused.schedule if job.fused is not None else {}
     pass_for = {str(k): v for k, v in getattr(job.fused, "pass_for", {}).items()} \
@@ -769,7 +813,7 @@ def main():
                      test_acc=test_acc, peak_hbm_gb=peak_gb, **halo)
 
     extra = {}
-    if not args.no_extra and not job.rehearse:
+    if args.full and not args.no_extra and not job.rehearse:
         ks = max(args.extra_steps, 1)
         if not head_restrict and not use_fused:
             t_ms, _, t_e = timed(job, ks, 1, True)
@@ -863,7 +907,7 @@ def main():
         job.free()
 
     shm = {}
-    if plan_splits is not None and not args.no_shmem_probe:
+    if args.full and plan_splits is not None and not args.no_shmem_probe:
         shm = shmem_probe_child(args, rank, world, plan_splits, dev)
     if args.rehearse_world > 1 and world == 1:
         # not a whole-job number: one rank's compute with a loopback exchange

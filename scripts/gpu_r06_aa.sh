@@ -4,7 +4,7 @@
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$R" && mkdir -p gpurun_out/r06
 for W in 2 4; do
-  DGRAPH_RCCL_SHARED_GPU=1 timeout -k 10 500 python -u bench.py --gpus $W --scale 0.02 --steps 2 \
+  DGRAPH_RCCL_SHARED_GPU=1 timeout -k 10 500 python -u bench.py --gpus $W --scale 0.02 --steps 2 --full \
     --warmup 1 --no-extra > gpurun_out/r06/bench_w${W}_shared_final.json 2> gpurun_out/r06/bench_w${W}_shared_final.err
   rc=$?; echo "== W=$W rc=$rc"
   case $rc in 0) ;; *) tail -20 gpurun_out/r06/bench_w${W}_shared_final.err; exit $rc;; esac

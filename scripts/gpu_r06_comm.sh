@@ -9,11 +9,11 @@ timeout -k 10 900 python -u -m pytest -x -v --timeout 300 --timeout-method threa
   tests/test_multidevice_gpu.py tests/test_comm_native_gpu.py tests/test_rccl_gpu.py \
   tests/test_multiproc_gpu.py > gpurun_out/r06/gpu_comm_tests.log 2>&1 || { echo "tests failed"; tail -40 gpurun_out/r06/gpu_comm_tests.log; exit 1; }
 tail -3 gpurun_out/r06/gpu_comm_tests.log
-DGRAPH_RCCL_SHARED_GPU=1 timeout -k 10 400 python -u bench.py --gpus 2 --scale 0.02 --steps 2 \
+DGRAPH_RCCL_SHARED_GPU=1 timeout -k 10 400 python -u bench.py --gpus 2 --scale 0.02 --steps 2 --full \
   --warmup 1 --no-extra > gpurun_out/r06/bench_w2_shared.json 2> gpurun_out/r06/bench_w2_shared.err \
   || { echo "w2 bench failed"; tail -30 gpurun_out/r06/bench_w2_shared.err; exit 1; }
 python -c "import json;d=json.loads(open('gpurun_out/r06/bench_w2_shared.json').read().splitlines()[-1]);print(json.dumps(d['shmem_probe']))"
-DGRAPH_RCCL_SHARED_GPU=1 timeout -k 10 500 python -u bench.py --gpus 8 --scale 0.02 --steps 2 \
+DGRAPH_RCCL_SHARED_GPU=1 timeout -k 10 500 python -u bench.py --gpus 8 --scale 0.02 --steps 2 --full \
   --warmup 1 --no-extra > gpurun_out/r06/bench_w8_shared.json 2> gpurun_out/r06/bench_w8_shared.err \
   || { echo "w8 bench failed"; tail -30 gpurun_out/r06/bench_w8_shared.err; exit 1; }
 python -c "import json;d=json.loads(open('gpurun_out/r06/bench_w8_shared.json').read().splitlines()[-1]);print(json.dumps(d['shmem_probe']))"

@@ -5,7 +5,8 @@ cd "$R"
 bash scripts/gpu_suite.sh
 rc=$?
 if [ $rc -ne 0 ] && [ $rc -ne 1 ]; then exit $rc; fi
-timeout -k 10 700 python -u bench.py > gpurun_out/bench_default.json 2> gpurun_out/bench_default.err
+O=${OUT:-bench_out}; mkdir -p "$O"
+timeout -k 10 700 python -u bench.py --full > "$O/bench_default.json" 2> "$O/bench_default.err"
 brc=$?
-echo "== bench rc=$brc"; tail -c 600 gpurun_out/bench_default.json
+echo "== bench rc=$brc"; tail -c 600 "$O/bench_default.json"
 exit $(( rc > brc ? rc : brc ))

@@ -8,6 +8,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -15,7 +17,7 @@ def test_bench_cli_w2_spawns_ranks_and_reports_regions(tmp_path):
     env = {k: v for k, v in os.environ.items()
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale", "2e-5",
-           "--steps", "2", "--warmup", "1", "--window", "64", "--extra-steps", "1"]
+           "--steps", "2", "--warmup", "1", "--window", "64", "--extra-steps", "1", "--full"]
     p = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -49,7 +51,7 @@ def test_bench_cli_shmem_probe_failure_keeps_headline(tmp_path):
            if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["DGRAPH_SHMEM_PROBE_FAULT"] = "abort1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scale", "2e-5",
-           "--steps", "1", "--warmup", "1", "--window", "64", "--no-extra",
+           "--steps", "1", "--warmup", "1", "--window", "64", "--full", "--no-extra",
            "--shmem-probe-timeout", "90"]
     p = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
@@ -59,6 +61,39 @@ def test_bench_cli_shmem_probe_failure_keeps_headline(tmp_path):
     assert d["value"] > 0 and d["n_gpus"] == 2
     failed = d["shmem_probe"]["failed"]
     assert any(f["rank"] == 1 and f["exit"] not in (0, None) for f in failed), failed
+
+
+def test_bench_cli_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """Without ``--full`` the line carries the headline only (no region breakdown, no
+    secondary jobs); ``--dump-outputs`` writes the last timed step's loss, hit counts,
+    updated weights and gradients as float .npy files."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items()
+           if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "2e-5",
+           "--steps", "1", "--warmup", "0", "--window", "64", "--dump-outputs", str(out)]
+    p = subprocess.run(cmd, cwd=tmp_path, env=env, capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == "edges_per_s" and d["unit"] == "edges/s" and d["higher_is_better"]
+    assert d["steps"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "fp32"
+    c = d["config"]
+    assert d["value"] == pytest.approx(c["num_layers"] * c["E_msg"] / (d["ms_per_step"] / 1e3))
+    for k in ("regions", "structureless", "bf16_stack", "train_rows_only", "xgmi_probe",
+              "shmem_probe"):
+        assert k not in d, k
+    files = {f.name: np.load(f) for f in out.iterdir()}
+    assert all(a.dtype in (np.float32, np.float64) for a in files.values())
+    assert float(files["loss.npy"][0]) == d["final_loss"]
+    assert files["correct_val_test.npy"].shape == (2,)
+    params = [n for n in files if n.startswith("param_")]
+    assert len(params) == 9 and sum(n.startswith("grad_") for n in files) == 9
+    assert files["param_00_layers_0_w_self.npy"].shape == (128, 256)
+    assert sum(a.nbytes for a in files.values()) <= 64 << 20
 
 
 def test_bench_cli_refuses_mismatched_world(tmp_path):

@@ -139,7 +139,8 @@ def test_bench_cli_shmem_probe_distinct_gpus():
     timeout, and a per-link rate."""
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     p = subprocess.run([sys.executable, "-u", os.path.join(repo, "bench.py"), "--gpus", "2",
-                        "--scale", "0.02", "--steps", "2", "--warmup", "1", "--no-extra"],
+                        "--scale", "0.02", "--steps", "2", "--warmup", "1", "--full",
+                        "--no-extra"],
                        cwd=repo, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.startswith('{"metric"')]

@@ -140,7 +140,7 @@ def test_bench_cli_two_ranks_rccl_shared_gpu():
     same loss as the W=1 run of the same (reduced-scale) graph."""
     common = ["--scale", "0.02", "--steps", "2", "--warmup", "1", "--no-extra"]
     w1 = _bench(["--gpus", "1"] + common, {})
-    w2 = _bench(["--gpus", "2"] + common, {"DGRAPH_RCCL_SHARED_GPU": "1"})
+    w2 = _bench(["--gpus", "2", "--full"] + common, {"DGRAPH_RCCL_SHARED_GPU": "1"})
     assert w2["n_gpus"] == 2 and w2["config"]["rccl_world_size"] == 2
     assert w2["config"]["process_group_backend"] == "nccl"
     assert w2["xgmi_probe"]["native_executor"]["bitwise_equal_to_torch"] is True
