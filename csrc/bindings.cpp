@@ -95,6 +95,92 @@ void spmm(const at::Tensor& rowptr, const at::Tensor& col, const c10::optional<a
                         cur_stream(x), cap, rmap));
 }
 
+// segment max / min with the winning slot, and its backward (see kernels.h)
+void check_arg(const at::Tensor& arg, const at::Tensor& like, const char* name) {
+  check_dev(arg, like, name);
+  check_rows(arg, name);
+  TORCH_CHECK(arg.scalar_type() == at::kInt, "dgraph_amd: ", name, " must be int32");
+  TORCH_CHECK(arg.size(0) == like.size(0) && arg.size(1) == like.size(1), "dgraph_amd: ",
+              name, " shape mismatch");
+}
+
+void segment_extreme_fwd_op(const at::Tensor& rowptr, const at::Tensor& col,
+                            const at::Tensor& x, const at::Tensor& out, const at::Tensor& arg,
+                            bool minimum, bool second,
+                            const c10::optional<at::Tensor>& row_map) {
+  check_dev(x, x, "x");
+  check_dev(rowptr, x, "rowptr");
+  check_dev(col, x, "col");
+  check_dev(out, x, "out");
+  check_rows(x, "x");
+  check_rows(out, "out");
+  check_arg(arg, out, "arg");
+  TORCH_CHECK(rowptr.scalar_type() == at::kLong && rowptr.is_contiguous(),
+              "rowptr must be contiguous int64");
+  TORCH_CHECK(col.is_contiguous(), "col must be contiguous");
+  TORCH_CHECK(x.scalar_type() == out.scalar_type(), "x/out dtype mismatch");
+  TORCH_CHECK(x.size(1) == out.size(1), "x/out feature mismatch");
+  const int64_t nrows = rowptr.numel() - 1;
+  const int64_t* rmap = nullptr;
+  if (row_map.has_value() && row_map->defined()) {
+    check_dev(*row_map, x, "row_map");
+    TORCH_CHECK(row_map->scalar_type() == at::kLong && row_map->is_contiguous() &&
+                    row_map->numel() == nrows,
+                "row_map must be contiguous int64 [nrows]");
+    rmap = row_map->data_ptr<int64_t>();
+  } else {
+    TORCH_CHECK(out.size(0) >= nrows, "out has fewer rows than the CSR");
+  }
+  const DType dt = dtype_of(x);
+  const IType it = itype_of(col);
+  if (nrows <= 0 || x.size(1) == 0) return;
+  // arg holds offsets within a row as int32 (and -2 - offset): every row must have fewer
+  // than 2^31 - 2 entries. Certain when the whole CSR does; else look at the degrees.
+  constexpr int64_t kMaxDeg = (int64_t(1) << 31) - 3;
+  if (col.numel() > kMaxDeg) {
+    const int64_t deg = (rowptr.slice(0, 1) - rowptr.slice(0, 0, nrows)).max().item<int64_t>();
+    TORCH_CHECK(deg <= kMaxDeg, "segment_extreme: a row of ", deg,
+                " entries does not fit the int32 winner offset");
+  }
+  c10::DeviceGuard g(x.device());
+  DG_HIP_CHECK(segment_extreme_fwd(dt, it, minimum, rowptr.data_ptr<int64_t>(), col.data_ptr(),
+                                   x.data_ptr(), x.stride(0), out.data_ptr(), out.stride(0),
+                                   arg.data_ptr<int32_t>(), arg.stride(0), nrows,
+                                   static_cast<int>(x.size(1)), second, rmap, cur_stream(x)));
+}
+
+void segment_extreme_bwd_op(const at::Tensor& t_rowptr, const at::Tensor& t_col,
+                            const at::Tensor& rel, const at::Tensor& g, const at::Tensor& arg,
+                            const at::Tensor& out, bool halo, double beta) {
+  check_dev(g, g, "g");
+  check_dev(t_rowptr, g, "t_rowptr");
+  check_dev(t_col, g, "t_col");
+  check_dev(rel, g, "rel");
+  check_dev(out, g, "out");
+  check_rows(g, "g");
+  check_rows(out, "out");
+  check_arg(arg, g, "arg");
+  TORCH_CHECK(t_rowptr.scalar_type() == at::kLong && t_rowptr.is_contiguous(),
+              "t_rowptr must be contiguous int64");
+  TORCH_CHECK(t_col.is_contiguous(), "t_col must be contiguous");
+  TORCH_CHECK(rel.scalar_type() == at::kInt && rel.is_contiguous() &&
+                  rel.numel() == t_col.numel(),
+              "rel must be contiguous int32, one per transposed entry");
+  TORCH_CHECK(g.scalar_type() == out.scalar_type(), "g/out dtype mismatch");
+  TORCH_CHECK(g.size(1) == out.size(1), "g/out feature mismatch");
+  const int64_t nrows = t_rowptr.numel() - 1;
+  TORCH_CHECK(out.size(0) >= nrows, "out has fewer rows than the transposed CSR");
+  const DType dt = dtype_of(g);
+  const IType it = itype_of(t_col);
+  if (nrows <= 0 || g.size(1) == 0) return;
+  c10::DeviceGuard guard(g.device());
+  DG_HIP_CHECK(segment_extreme_bwd(dt, it, t_rowptr.data_ptr<int64_t>(), t_col.data_ptr(),
+                                   rel.data_ptr<int32_t>(), g.data_ptr(), g.stride(0),
+                                   arg.data_ptr<int32_t>(), arg.stride(0), out.data_ptr(),
+                                   out.stride(0), nrows, static_cast<int>(g.size(1)), halo,
+                                   static_cast<float>(beta), cur_stream(g)));
+}
+
 // hub-row splitting passes (see kernels.h): fp32 partial sums of the hub-row tails, then
 // their fixed-order reduction into the output rows
 void spmm_hub_partials_op(const at::Tensor& seg_beg, const at::Tensor& seg_end,
@@ -774,6 +860,10 @@ TORCH_LIBRARY(dgraph_amd, m) {
         "Tensor? col_scale, Tensor x, Tensor(a!) partials) -> ()");
   m.def("spmm_hub_reduce(Tensor partials, Tensor hub_seg_ptr, Tensor hub_rows, "
         "Tensor? row_scale, Tensor(a!) out) -> ()");
+  m.def("segment_extreme_fwd(Tensor rowptr, Tensor col, Tensor x, Tensor(a!) out, "
+        "Tensor(b!) arg, bool minimum, bool second, Tensor? row_map=None) -> ()");
+  m.def("segment_extreme_bwd(Tensor t_rowptr, Tensor t_col, Tensor rel, Tensor g, Tensor arg, "
+        "Tensor(a!) out, bool halo, float beta) -> ()");
   m.def("copy_rows(Tensor x, Tensor? src_idx, Tensor? dst_idx, Tensor(a!) out, "
         "bool accumulate) -> ()");
   m.def("masked_gather_rows(Tensor x, Tensor idx, Tensor mask, int value, Tensor(a!) out) -> ()");
@@ -785,6 +875,8 @@ TORCH_LIBRARY_IMPL(dgraph_amd, CUDA, m) {
   m.impl("spmm", &dgraph::spmm);
   m.impl("spmm_hub_partials", &dgraph::spmm_hub_partials_op);
   m.impl("spmm_hub_reduce", &dgraph::spmm_hub_reduce_op);
+  m.impl("segment_extreme_fwd", &dgraph::segment_extreme_fwd_op);
+  m.impl("segment_extreme_bwd", &dgraph::segment_extreme_bwd_op);
   m.impl("copy_rows", &dgraph::copy_rows_op);
   m.impl("masked_gather_rows", &dgraph::masked_gather_rows_op);
   m.impl("edge_softmax_fwd", &dgraph::edge_softmax_fwd_op);

@@ -118,6 +118,28 @@ hipError_t spmm_hub_reduce(DType dt, const float* partials, const int64_t* hub_s
                            int64_t ldo, int64_t nhub, int F, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
+// CSR segment max / min with a recorded winner (spmm_max.hip).
+//   out[r, f] = max (min) over k in [rowptr[r], rowptr[r+1]) of x[col[k], f]; 0 for an
+//   empty row. arg[r, f] (int32) = k - rowptr[r] of the FIRST slot attaining it, -1 for an
+//   empty row. second: out / arg hold an incumbent (an earlier pass over another source);
+//   an entry replaces it only where strictly better (or where there is none) and is
+//   recorded as -2 - offset. row_map as in spmm_csr. A row's entry count must fit int32.
+// Backward, over the transposed pattern (row c = source, t_col = destination rows, rel =
+// each entry's forward offset within its destination row):
+//   out[c, f] = beta * out[c, f] + sum over k of g[t_col[k], f] where
+//   arg[t_col[k], f] == rel[k]  (halo: == -2 - rel[k]); fp32 accumulate, fixed order.
+// ---------------------------------------------------------------------------
+hipError_t segment_extreme_fwd(DType dt, IType it, bool minimum, const int64_t* rowptr,
+                               const void* col, const void* x, int64_t ldx, void* out,
+                               int64_t ldo, int32_t* arg, int64_t lda, int64_t nrows, int F,
+                               bool second, const int64_t* row_map, hipStream_t stream);
+hipError_t segment_extreme_bwd(DType dt, IType it, const int64_t* t_rowptr, const void* t_col,
+                               const int32_t* rel, const void* g, int64_t ldg,
+                               const int32_t* arg, int64_t lda, void* out, int64_t ldo,
+                               int64_t nrows, int F, bool halo, float beta,
+                               hipStream_t stream);
+
+// ---------------------------------------------------------------------------
 // Row copy with optional source and destination index (K4/K7/K8 replacement, K-new-1).
 //   out[dst(i)] (+)= x[src(i)]   for i in [0, n)
 // src/dst null == identity. src(i) < 0 writes zeros; dst(i) < 0 skips the row.

@@ -31,7 +31,7 @@ from ..ops import kernels as K
 from ..parallel import halo_recompute as _hr
 from ..ops.dense import (col_sum_f32, dual_gemm, dual_gemm_shape_ok, mm_f32,  # noqa: F401
                          tile32_mask_words, wgrad)
-from ..parallel.dist_graph import DistGraph
+from ..parallel.dist_graph import DistGraph, dist_aggregate
 
 
 class SAGELayerFn(Function):
@@ -105,11 +105,18 @@ class SAGELayerFn(Function):
 
 
 class SAGEConv(nn.Module):
-    """One GraphSAGE-mean layer over a :class:`DistGraph`."""
+    """One GraphSAGE layer over a :class:`DistGraph`: the mean aggregator by default;
+    ``aggr="max"`` / ``"min"`` take the elementwise extremum over the in-neighbours
+    (GraphSAGE-pool style, not degree-biased), always aggregate-first."""
 
     def __init__(self, in_dim: int, out_dim: int, bias: bool = True, relu: bool = True,
-                 order: str = "auto", save_agg: Optional[bool] = None):
+                 order: str = "auto", save_agg: Optional[bool] = None, aggr: str = "mean"):
         super().__init__()
+        if aggr not in ("mean", "max", "min"):
+            raise ValueError(f"unsupported aggr {aggr!r}")
+        if aggr != "mean" and order == "project_first":
+            raise ValueError(f"aggr={aggr!r} is not linear: it cannot run project_first")
+        self.aggr = aggr
         self.in_dim, self.out_dim, self.relu = in_dim, out_dim, relu
         self.w_self = nn.Parameter(torch.empty(in_dim, out_dim))
         self.w_neigh = nn.Parameter(torch.empty(in_dim, out_dim))
@@ -132,6 +139,15 @@ class SAGEConv(nn.Module):
         return self.order == "project_first"
 
     def forward(self, x: torch.Tensor, graph: DistGraph) -> torch.Tensor:
+        if self.aggr != "mean":
+            # composed from autograd ops: the extremum is not linear, so neither the
+            # project-first order nor SAGELayerFn's single-SpMM backward applies
+            dt = x.dtype
+            a = dist_aggregate(x, graph, reduce=self.aggr)
+            y = x @ self.w_self.to(dt) + a @ self.w_neigh.to(dt)
+            if self.bias is not None:
+                y = y + self.bias.to(dt)
+            return y.relu() if self.relu else y
         save = self.save_agg
         if save is None:
             save = _auto_save_agg(x, graph)
@@ -657,18 +673,21 @@ class SAGEStackFn(Function):
 
 
 class GraphSAGE(nn.Module):
-    """``num_layers`` SAGE-mean layers (ReLU between, none after the last) -> logits.
+    """``num_layers`` SAGE layers (ReLU between, none after the last) -> logits.
 
-    With ``dropout == 0`` the forward runs as one :class:`SAGEStackFn` node (buffer
-    recycling, bit masks); otherwise as per-layer :class:`SAGEConv` nodes.
+    With the mean aggregator and ``dropout == 0`` the forward runs as one
+    :class:`SAGEStackFn` node (buffer recycling, bit masks); otherwise, and always with
+    ``aggr="max"`` / ``"min"``, as per-layer :class:`SAGEConv` nodes.
     """
 
     def __init__(self, in_dim: int, hidden: int, out_dim: int, num_layers: int = 3,
-                 dropout: float = 0.0, save_agg: Optional[bool] = None):
+                 dropout: float = 0.0, save_agg: Optional[bool] = None, aggr: str = "mean"):
         super().__init__()
         dims = [in_dim] + [hidden] * (num_layers - 1) + [out_dim]
+        self.aggr = aggr
         self.layers = nn.ModuleList(
-            SAGEConv(dims[i], dims[i + 1], relu=(i < num_layers - 1), save_agg=save_agg)
+            SAGEConv(dims[i], dims[i + 1], relu=(i < num_layers - 1), save_agg=save_agg,
+                     aggr=aggr)
             for i in range(num_layers)
         )
         self.dropout = dropout
@@ -685,7 +704,7 @@ class GraphSAGE(nn.Module):
         validation/test vertices from the same full-graph forward (no gradient).
         ``restrict_last=True`` aggregates only ``out_rows`` in a project-first output layer
         (train-rows-only step; not a full-graph forward, see :class:`SAGEStackFn`)."""
-        if self.dropout == 0 or not self.training:
+        if self.aggr == "mean" and (self.dropout == 0 or not self.training):
             specs = tuple((l.relu, l.project_first()) for l in self.layers)
             params = []
             for l in self.layers:

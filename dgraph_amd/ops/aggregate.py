@@ -59,6 +59,26 @@ class _AggregateFn(Function):
         return gx, None, gw, None, None
 
 
+class _AggregateExtremeFn(Function):
+    """Max / min over each row's entries. The forward records the winning CSR slot per
+    ``(row, feature)`` (the first that attains the extremum); the backward routes the whole
+    of ``g[r, f]`` to that slot's source row, as a gather over the transposed pattern."""
+
+    @staticmethod
+    def forward(ctx, x, csr: CSR, minimum: bool):
+        out, arg = K.segment_extreme(csr.rowptr, csr.col, x, minimum=minimum)
+        ctx.csr = csr
+        ctx.save_for_backward(arg)
+        ctx.mark_non_differentiable(arg)
+        return out, arg
+
+    @staticmethod
+    def backward(ctx, g, _g_arg=None):
+        (arg,) = ctx.saved_tensors
+        t, rel = ctx.csr.transpose_rel()
+        return K.segment_extreme_bwd(t.rowptr, t.col, rel, g.contiguous(), arg), None, None
+
+
 def aggregate(
     x: torch.Tensor,
     csr: CSR,
@@ -70,7 +90,19 @@ def aggregate(
 
     ``edge_weight`` is ``[nnz]`` or ``[nnz, heads]`` in CSR slot order; with heads > 1
     the feature dim is split into ``heads`` equal slices, each scaled by its head weight.
+
+    ``reduce="max"`` / ``"min"``: the elementwise extremum over a row's entries (0 for an
+    empty row), unweighted and single-head. Its gradient goes to ONE entry per
+    ``(row, feature)``: the first in CSR slot order that attains the extremum.
     """
+    if reduce in ("max", "min"):
+        if edge_weight is not None:
+            raise ValueError(f"reduce={reduce!r} takes no edge weights")
+        if heads != 1:
+            raise ValueError(f"reduce={reduce!r} takes one head, got heads={heads}")
+        if x.stride(1) != 1 and x.shape[1] > 1:  # a row stride is fine, a feature stride not
+            x = x.contiguous()
+        return _AggregateExtremeFn.apply(x, csr, reduce == "min")[0]
     if reduce not in ("sum", "mean"):
         raise ValueError(f"unsupported reduce {reduce!r}")
     ew = None

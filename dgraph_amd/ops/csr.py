@@ -68,6 +68,10 @@ class CSR:
     # row-compacted CSR (see compact_rows): CSR row r is output row row_map[r]
     row_map: Optional[torch.Tensor] = None
     _compact: Optional["CSR"] = field(default=None, repr=False)
+    # (transposed CSR, rel) of transpose_rel(); _perm_to_parent marks a CSR built by
+    # transpose(), whose perm maps its slots to the parent's slots
+    _transpose_rel: Optional[tuple] = field(default=None, repr=False)
+    _perm_to_parent: bool = field(default=False, repr=False)
 
     @property
     def num_rows(self) -> int:
@@ -159,11 +163,13 @@ class CSR:
     def to(self, device) -> "CSR":
         """Move to ``device``, keeping the cached transpose (and its back link)."""
         new = self._moved(device)
+        new._perm_to_parent = self._perm_to_parent
         t = self._transpose
         if t is self:
             new._transpose = new
         elif t is not None:
             nt = t._moved(device)
+            nt._perm_to_parent = t._perm_to_parent
             nt._transpose = new
             new._transpose = nt
         return new
@@ -207,15 +213,35 @@ class CSR:
                 # Same structure; slot k of A^T is slot k of A only as a pattern.
                 self._transpose = self
             else:
-                cols = self.col.long()
-                ct, perm = torch.sort(cols, stable=True)
-                rows = self.row_ids()[perm]
-                rowptr = _rowptr_from_sorted_rows(ct, self.num_cols)
-                t = CSR(rowptr, rows.to(index_dtype_for(self.num_rows)).contiguous(),
-                        self.num_rows, perm)
+                t = self._build_transpose()
                 t._transpose = self
                 self._transpose = t
         return self._transpose
+
+    def _build_transpose(self) -> "CSR":
+        cols = self.col.long()
+        ct, perm = torch.sort(cols, stable=True)
+        rows = self.row_ids()[perm]
+        rowptr = _rowptr_from_sorted_rows(ct, self.num_cols)
+        t = CSR(rowptr, rows.to(index_dtype_for(self.num_rows)).contiguous(),
+                self.num_rows, perm)
+        t._perm_to_parent = True
+        return t
+
+    def transpose_rel(self) -> tuple["CSR", torch.Tensor]:
+        """``(t, rel)`` for the backward of a max / min aggregation (cached): ``t`` is the
+        transposed pattern with a slot map (:meth:`transpose`, or one built here for a
+        ``symmetric`` CSR, whose transpose is the pattern alone), and ``rel[k]`` (int32) the
+        offset of ``t``'s slot ``k`` within its row of THIS CSR:
+        ``rel = t.perm - rowptr[t.col]``."""
+        if self._transpose_rel is None:
+            t = self._transpose if (self._transpose is not None or self.symmetric) \
+                else self.transpose()
+            if t is None or t is self or not t._perm_to_parent or t._transpose is not self:
+                t = self._build_transpose()
+            rel = (t.perm - self.rowptr[t.col.long()]).to(torch.int32).contiguous()
+            self._transpose_rel = (t, rel)
+        return self._transpose_rel
 
     def select_rows(self, rows: torch.Tensor) -> "CSR":
         """CSR of the row subset ``rows`` (in that order; columns unchanged). Used for the

@@ -91,6 +91,66 @@ def spmm(
     return out
 
 
+def segment_extreme(
+    rowptr: torch.Tensor,
+    col: torch.Tensor,
+    x: torch.Tensor,
+    out: Optional[torch.Tensor] = None,
+    arg: Optional[torch.Tensor] = None,
+    *,
+    minimum: bool = False,
+    second: bool = False,
+    row_map: Optional[torch.Tensor] = None,
+):
+    """Segment max (``minimum``: min) over the CSR rows with the winning slot:
+    ``out[r, f] = max_k x[col[k], f]`` (0 for an empty row) and ``arg[r, f]`` (int32) = the
+    offset within row ``r`` of the FIRST slot that attains it (-1 for an empty row).
+
+    ``second``: ``out`` / ``arg`` hold the result of an earlier pass over another source
+    (the interior block); an entry of this pass replaces it only where strictly better, and
+    is recorded as ``-2 - offset``. ``row_map`` as in :func:`spmm`. Returns ``(out, arg)``."""
+    R = rowptr.numel() - 1
+    F = x.shape[1]
+    if (second or row_map is not None) and (out is None or arg is None):
+        raise ValueError("segment_extreme: second / row_map need explicit out and arg")
+    if out is None:
+        out = torch.empty(R, F, dtype=x.dtype, device=x.device)
+    if arg is None:
+        arg = torch.empty(out.shape[0], F, dtype=torch.int32, device=x.device)
+    if _native_ok(x):
+        _native.ops().segment_extreme_fwd(rowptr, col, x, out, arg, bool(minimum),
+                                          bool(second), row_map)
+        return out, arg
+    return _ref.segment_extreme(rowptr, col, x, out, arg, minimum, second, row_map)
+
+
+def segment_extreme_bwd(
+    t_rowptr: torch.Tensor,
+    t_col: torch.Tensor,
+    rel: torch.Tensor,
+    g: torch.Tensor,
+    arg: torch.Tensor,
+    out: Optional[torch.Tensor] = None,
+    *,
+    halo: bool = False,
+    beta: float = 0.0,
+) -> torch.Tensor:
+    """Backward of :func:`segment_extreme` as a gather over the transposed pattern
+    (``t_rowptr`` / ``t_col``: rows = source rows, columns = destination rows; ``rel[k]``:
+    entry k's offset within its destination row, :meth:`CSR.transpose_rel`):
+    ``out[c] = beta * out[c] + sum_k g[t_col[k]] * [arg[t_col[k]] == rel[k]]``
+    (``halo``: ``== -2 - rel[k]``). No atomics; fixed summation order."""
+    C = t_rowptr.numel() - 1
+    if out is None:
+        out = torch.empty(C, g.shape[1], dtype=g.dtype, device=g.device)
+        beta = 0.0
+    if _native_ok(g):
+        _native.ops().segment_extreme_bwd(t_rowptr, t_col, rel, g, arg, out, bool(halo),
+                                          float(beta))
+        return out
+    return _ref.segment_extreme_bwd(t_rowptr, t_col, rel, g, arg, out, halo, beta)
+
+
 def copy_rows(
     x: torch.Tensor,
     src_idx: Optional[torch.Tensor] = None,

@@ -99,6 +99,69 @@ def spmm_hub_reduce(partials, hub_seg_ptr, hub_rows, out, row_scale=None):
     return out
 
 
+_NO_SLOT = 2**62
+
+
+def segment_extreme(rowptr, col, x, out, arg, minimum=False, second=False, row_map=None):
+    """Segment max (min) with the winning slot (cf. kernels.h). ``out[r, f]`` is the extremum
+    of ``x[col[k], f]`` over row ``r``'s slots (0 for an empty row) and ``arg[r, f]`` the
+    offset ``k - rowptr[r]`` of the FIRST slot attaining it (-1 for an empty row): a
+    lexicographic (value, slot) reduction. ``second``: ``out`` / ``arg`` hold an incumbent,
+    replaced only where this pass is strictly better (or there is none), recorded as
+    ``-2 - offset``. ``row_map``: CSR row ``r`` is output row ``row_map[r]``."""
+    R = rowptr.numel() - 1
+    F = x.shape[1]
+    if R <= 0 or F == 0:
+        return out, arg
+    dev = x.device
+    cdt = torch.float64 if x.dtype == torch.float64 else torch.float32
+    rows = _row_ids(rowptr)
+    vals = x.to(cdt)[col.long()]  # widening is exact; the comparisons see the same order
+    if minimum:
+        vals = -vals
+    idx = rows.unsqueeze(1).expand(-1, F)
+    best = torch.full((R, F), float("-inf"), dtype=cdt, device=dev)
+    best.scatter_reduce_(0, idx, vals, "amax", include_self=True)
+    off = (torch.arange(rows.numel(), device=dev) - rowptr[:-1].long()[rows]).unsqueeze(1)
+    cand = torch.where(vals == best[rows], off, _NO_SLOT)  # +0.0 == -0.0: a tie
+    first = torch.full((R, F), _NO_SLOT, dtype=torch.long, device=dev)
+    first.scatter_reduce_(0, idx, cand, "amin", include_self=True)
+    has = first < _NO_SLOT
+    tgt = slice(0, R) if row_map is None else row_map.long()
+    if second:
+        old = out[tgt].to(cdt)
+        old_arg = arg[tgt]
+        win = has & ((old_arg == -1) | (best > (-old if minimum else old)))
+        new_out = torch.where(win, -best if minimum else best, old)
+        new_arg = torch.where(win, -2 - first, old_arg.long())
+    else:
+        new_out = torch.where(has, -best if minimum else best, torch.zeros((), dtype=cdt))
+        new_arg = torch.where(has, first, -1)
+    out[tgt] = new_out.to(out.dtype)
+    arg[tgt] = new_arg.to(arg.dtype)
+    return out, arg
+
+
+def segment_extreme_bwd(t_rowptr, t_col, rel, g, arg, out, halo=False, beta=0.0):
+    """Backward of :func:`segment_extreme` over the transposed pattern: source row ``c``
+    sums ``g[r, f]`` over its entries ``(r = t_col[k], rel[k])`` that ``arg[r, f]`` names
+    (``-2 - rel[k]`` for the halo block). fp32 accumulate (fp64 for fp64)."""
+    C = t_rowptr.numel() - 1
+    if C <= 0 or g.shape[1] == 0:
+        return out
+    cdt = torch.float64 if g.dtype == torch.float64 else torch.float32
+    src = _row_ids(t_rowptr)
+    r = t_col.long()
+    key = (-2 - rel.long()) if halo else rel.long()
+    hit = arg[r].long() == key.unsqueeze(1)
+    acc = torch.zeros(C, g.shape[1], dtype=cdt, device=g.device)
+    acc.index_add_(0, src, torch.where(hit, g.to(cdt)[r], torch.zeros((), dtype=cdt)))
+    if beta != 0.0:
+        acc = acc + beta * out[:C].to(cdt)
+    out[:C] = acc.to(out.dtype)
+    return out
+
+
 def copy_rows(
     x: torch.Tensor,
     src_idx: Optional[torch.Tensor],

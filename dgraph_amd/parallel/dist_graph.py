@@ -379,6 +379,83 @@ class DistGraph:
             K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
         return out
 
+    def aggregate_extreme(self, x: torch.Tensor, minimum: bool = False,
+                          out: Optional[torch.Tensor] = None,
+                          halo_rows: Optional[torch.Tensor] = None):
+        """Elementwise max (``minimum``: min) over in-neighbours, local and halo, on the
+        schedule of :meth:`aggregate`: the interior pass runs while the halo rows are on the
+        links, then the halo block is applied as a second source. Returns ``(out, arg)``;
+        ``arg[r, f]`` (int32) names the winning entry: ``>= 0`` its offset in the interior
+        row, ``<= -2`` the halo row's entry ``-2 - arg``, ``-1`` no entry. Interior entries
+        come first: a halo entry wins only if strictly better. ``halo_rows`` as in
+        :meth:`aggregate` (no exchange)."""
+        self.edges_aggregated += self.nnz
+        F = x.shape[1]
+        it = self.interior
+        if out is None:
+            out = torch.empty(self.L, F, dtype=x.dtype, device=x.device)
+        arg = torch.empty(out.shape[0], F, dtype=torch.int32, device=x.device)
+        if self.halo is None:
+            return K.segment_extreme(it.rowptr, it.col, x, out, arg, minimum=minimum)
+        hc = self.halo.compact_rows()
+        if halo_rows is not None:
+            K.segment_extreme(it.rowptr, it.col, x, out, arg, minimum=minimum)
+            return K.segment_extreme(hc.rowptr, hc.col, halo_rows, out, arg, minimum=minimum,
+                                     second=True, row_map=hc.row_map)
+        # the exchanges depend on the plan alone (a rank with sends and no halo row posts
+        # them too); column chunks as in aggregate()
+        pend = []
+        for c0, c1 in self._col_chunks(self.a2a, F, x.element_size()):
+            xc = x if (c0, c1) == (0, F) else x[:, c0:c1]
+            recv, work = self.a2a(K.gather_rows(xc, self.send_map.idx), async_op=True)
+            if not self.overlap:
+                work.wait()
+            pend.append((c0, c1, recv, work))
+        K.segment_extreme(it.rowptr, it.col, x, out, arg, minimum=minimum)
+        for c0, c1, recv, work in pend:
+            work.wait()
+            whole = (c0, c1) == (0, F)
+            K.segment_extreme(hc.rowptr, hc.col, recv, out if whole else out[:, c0:c1],
+                              arg if whole else arg[:, c0:c1], minimum=minimum, second=True,
+                              row_map=hc.row_map)
+        return out, arg
+
+    def aggregate_extreme_T(self, g: torch.Tensor, arg: torch.Tensor,
+                            out: Optional[torch.Tensor] = None,
+                            halo_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Backward of :meth:`aggregate_extreme`: ``g[r, f]`` goes, whole, to the source of
+        the entry ``arg[r, f]`` names. Interior winners are gathered over the interior's
+        transposed pattern (always the real transpose: ``arg`` is not symmetric even when
+        the pattern is), halo winners over the halo block's into ``[H, F]`` rows, which
+        then take the reverse path of :meth:`aggregate_T` (reverse exchange, owner-side
+        segment sum). ``halo_out``: ``[H, F]`` buffer that keeps the halo gradient here."""
+        g = g.contiguous()
+        F = g.shape[1]
+        it, irel = self.interior.transpose_rel()
+        self.edges_aggregated += it.nnz + (self.halo.nnz if self.halo is not None else 0)
+        if self.halo is None:
+            return K.segment_extreme_bwd(it.rowptr, it.col, irel, g, arg, out)
+        ht, hrel = self.halo.transpose_rel()
+        if halo_out is not None:
+            K.segment_extreme_bwd(ht.rowptr, ht.col, hrel, g, arg, halo_out, halo=True)
+            return K.segment_extreme_bwd(it.rowptr, it.col, irel, g, arg, out)
+        pend = []
+        for c0, c1 in self._col_chunks(self.a2a_rev, F, g.element_size()):
+            whole = (c0, c1) == (0, F)
+            hg = K.segment_extreme_bwd(ht.rowptr, ht.col, hrel, g if whole else g[:, c0:c1],
+                                       arg if whole else arg[:, c0:c1], halo=True)
+            sg, work = self.a2a_rev(hg, async_op=True)
+            if not self.overlap:
+                work.wait()
+            pend.append((c0, c1, sg, work))
+        out = K.segment_extreme_bwd(it.rowptr, it.col, irel, g, arg, out)
+        st = self.send_map.transpose_csr().compact_rows()
+        for c0, c1, sg, work in pend:
+            work.wait()
+            oc = out if (c0, c1) == (0, F) else out[:, c0:c1]
+            K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
+        return out
+
     def _peers(self) -> bool:
         """True when the plan's peers exist (a process group of the plan's size)."""
         import torch.distributed as dist
@@ -591,6 +668,27 @@ class _DistAggregateFn(Function):
         return ctx.graph.aggregate_T(g, ctx.mean), None, None
 
 
-def dist_aggregate(x: torch.Tensor, graph: DistGraph, mean: bool = True) -> torch.Tensor:
-    """Autograd-aware distributed neighbourhood aggregation (sum or mean)."""
-    return _DistAggregateFn.apply(x, graph, mean)
+class _DistAggregateExtremeFn(Function):
+    @staticmethod
+    def forward(ctx, x, graph: DistGraph, minimum: bool):
+        out, arg = graph.aggregate_extreme(x.contiguous(), minimum)
+        ctx.graph = graph
+        ctx.save_for_backward(arg)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (arg,) = ctx.saved_tensors
+        return ctx.graph.aggregate_extreme_T(g, arg), None, None
+
+
+def dist_aggregate(x: torch.Tensor, graph: DistGraph, mean: bool = True,
+                   reduce: Optional[str] = None) -> torch.Tensor:
+    """Autograd-aware distributed neighbourhood aggregation: sum or mean (``mean``), or
+    with ``reduce="max"`` / ``"min"`` the elementwise extremum over the in-neighbours (its
+    gradient goes to the one winning entry, :meth:`DistGraph.aggregate_extreme`)."""
+    if reduce is None:
+        return _DistAggregateFn.apply(x, graph, mean)
+    if reduce not in ("max", "min"):
+        raise ValueError(f"unsupported reduce {reduce!r}")
+    return _DistAggregateExtremeFn.apply(x, graph, reduce == "min")
