@@ -3,7 +3,8 @@
 passes (rocprofv3 --pmc) and per-kernel timing:
 
 * spmm_f32_rowgroup (64-column passes) over the papers100M-shaped CSR at F = 128 and 256;
-* the column-mapped (CMAP) transposed aggregation of a gradient stored on ~30 % of rows;
+* the column-mapped (CMAP) transposed aggregation of a gradient stored on ~30 % of rows,
+  alone and with the gate + self-term epilogue of the input-layer backward;
 * gemm_f32 dual GEMM K = 256 + 256, N = 256 (hidden layer) and N = 176 (output layer);
 * wgrad_f32 [K = 256, N = 256] over a row chunk.
 
@@ -84,7 +85,14 @@ def main():
         for pc in (64, 128, 256):
             timed(f"spmm_f32_cmap_F256_pc{pc}{sfx}", lambda pc=pc: F32.spmm_f32(
                 csr.rowptr, csr.col, u, out, col_map=smap, pass_cols=pc))
-        del u, out
+        # the same pass as the input-layer backward runs it: full width, the ReLU gate and the
+        # support rows' own term in its epilogue
+        gate = torch.randn(L, 256, device=dev)
+        v = torch.randn(S.numel(), 256, device=dev)
+        timed(f"spmm_f32_cmap_gate_self_F256_pc256{sfx}", lambda: F32.spmm_f32(
+            csr.rowptr, csr.col, u, out, col_map=smap, pass_cols=256, gate=gate, self_add=v,
+            self_map=smap))
+        del u, v, gate, out
     _native.ops().set_f32_sched(-1, -1, 0)
     if a.spmm_only:
         print(json.dumps(res))

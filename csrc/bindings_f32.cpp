@@ -148,10 +148,13 @@ void spmm_f32_ex_op(const at::Tensor& rowptr, const at::Tensor& col,
     const int64_t max_out = rmap ? out.size(0) : nrows;
     TORCH_CHECK(self_row0 >= 0 && self_row0 + max_out <= sm->numel(),
                 "self_map too short for self_row0 + output rows");
-    a.self_add = sa->data_ptr<float>();
-    a.self_map = sm->data_ptr<int32_t>();
-    a.ld_self = sa->stride(0);
-    a.self_row0 = self_row0;
+    // (a self term without rows adds nothing: left out, so the kernel may read row 0)
+    if (sa->size(0) > 0) {
+      a.self_add = sa->data_ptr<float>();
+      a.self_map = sm->data_ptr<int32_t>();
+      a.ld_self = sa->stride(0);
+      a.self_row0 = self_row0;
+    }
   }
   a.row_ids = rid;
   a.row_map = rmap;

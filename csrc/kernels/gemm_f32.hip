@@ -39,6 +39,24 @@
 //     share after everyone else); tile indices are fetched a tile ahead, and the next
 //     tile's first stage is loaded during the current tile's last stage, so the prologue's
 //     global latency and the epilogue's stores overlap MFMAs.
+//
+// In place (a contract the fused executor relies on: models/sage_fused.py, the boundary-row
+// store and the reused layer-0 aggregate): A2 may alias ``out`` — the same rows, any column
+// range of them, e.g. A2 = out[:, :K2] with lda2 = ldo — when o_rows is null. Why it holds:
+//   * a tile's A2 rows are read only by the block that owns the tile (a block owns 256 rows
+//     x ALL N columns; rows past M clamp to row M - 1, which is in the last tile itself);
+//   * that block stages every K stage of the tile into LDS, each retired by vmcnt(0) + a
+//     barrier, before its epilogue stores the first element of the tile;
+//   * the load that runs across the epilogue's stores is the NEXT tile's first stage (or a
+//     re-read of this tile's first stage for the block's last tile), and stage 0 always
+//     reads A1 (K1 >= 32), never A2; the dynamic tile counter only changes WHICH block owns
+//     a tile, and every tile is handed out once.
+// The same holds for a dense A1 (a_rows null): the prefetched rows are those of a tile this
+// block owns and has not stored yet. Not in place: A1 through a_rows (a gathered row may sit
+// in another block's tile), or o_rows (the stores leave the tile's rows). cin and gate may
+// alias out (read per element by the thread that writes it). N > 256 runs as several
+// launches over column blocks: the caller copies an aliasing operand first (ops/f32.py).
+// tests/test_reuse_agg0_gpu.py holds the A2 = out[:, :K2] case, bitwise.
 #include "../common.h"
 #include "kernels.h"
 #include "lds_dma.h"

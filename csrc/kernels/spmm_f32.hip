@@ -26,6 +26,17 @@
 //     pass when the halo is resident, instead of an interior pass plus a beta=1 halo pass.
 //     With a col_map the split applies to the mapped index (a support-row gradient and the
 //     received support rows of the halo, one map over local + halo columns).
+//   * gate + self term together (compile-time GS; the launcher picks it for a column-mapped
+//     call that has gate, self_add and no row_map — the input-layer gradient pass): the
+//     generic epilogue runs self_map[row] -> self_add row -> gate row as three serialized
+//     round trips after the last FMA. GS loads self_map[row] at the top of the row, next to
+//     the rowptr loads (1 VGPR, hidden behind the index -> gather chain), and then issues
+//     the self_add row (row 0 when the row has none: valid, unbranched) and the gate row
+//     together: one round trip. Same operations in the same order: bitwise the generic path.
+//     78 VGPRs at 64 lanes per row, 6 waves per SIMD, as the generic variant. (Loading the
+//     two rows at the top as well costs 8 VGPRs and a wave of occupancy and gains less;
+//     row_scale or the beta != 0 old row at the top of the plain pass gain nothing at the
+//     step level: PERFORMANCE.md.)
 // Accumulation fp32 with packed FMAs in a fixed order per row: bitwise deterministic.
 #include "../common.h"
 #include "kernels.h"
@@ -39,7 +50,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 // batch of all LPR rows (all loads of a chunk before its FMAs: -3 %) and against forcing 6 or
 // 8 waves per SIMD (fewer registers, fewer loads in flight: -28 % / -38 %),
 // profiles/r04/spmm_f32_variants_ab.log.
-template <typename IdxT, int LPR, int WMODE, bool CMAP, bool TWO, bool KB = false>
+template <typename IdxT, int LPR, int WMODE, bool CMAP, bool TWO, bool KB = false,
+          bool GS = false>
 __global__ __launch_bounds__(256) void spmm_f32_rowgroup_kernel(SpmmF32Args a) {
   constexpr int VEC = 4;
   constexpr int G = kWave / LPR;
@@ -94,6 +106,10 @@ __global__ __launch_bounds__(256) void spmm_f32_rowgroup_kernel(SpmmF32Args a) {
     const int64_t s = has_row ? rowptr[rr] : 0;
     const int64_t deg1 = has_row ? (a.rowend ? a.rowend[rr] : rowptr[rr + 1]) - s : 0;
     const int deg = static_cast<int>(deg1 > cap ? cap : deg1);
+    // GS: the row's self-term index, in flight with the rowptr loads (row 0 for a lane
+    // without a row: nrows > 0, so valid)
+    int32_t m_top = -1;
+    if constexpr (GS) m_top = a.self_map[a.self_row0 + (has_row ? r : 0)];
     int maxdeg = deg;
 #pragma unroll
     for (int off = LPR; off < kWave; off <<= 1) {
@@ -208,7 +224,7 @@ __global__ __launch_bounds__(256) void spmm_f32_rowgroup_kernel(SpmmF32Args a) {
       my_c = nx_c;
     }
     if (has_row && active) {
-      const int64_t orow = a.row_map ? a.row_map[r] : r;
+      const int64_t orow = (!GS && a.row_map) ? a.row_map[r] : r;  // GS: no row_map
       const float rs = a.row_scale ? a.row_scale[orow] : 1.f;
       float* o = a.out + orow * a.ldo + f;
       const float beta = a.beta;
@@ -225,7 +241,21 @@ __global__ __launch_bounds__(256) void spmm_f32_rowgroup_kernel(SpmmF32Args a) {
         res.z = acc[1].x * rs;
         res.w = acc[1].y * rs;
       }
-      if (a.self_add) {  // + the row's own term, stored row-compacted (row-uniform branch)
+      if constexpr (GS) {
+        // both rows in flight together; the self row is selected, not branched around
+        const float4 sv = *reinterpret_cast<const float4*>(
+            a.self_add + static_cast<int64_t>(m_top >= 0 ? m_top : 0) * a.ld_self + f);
+        const float4 gv = *reinterpret_cast<const float4*>(a.gate + orow * a.ldgate + f);
+        res.x = m_top >= 0 ? res.x + sv.x : res.x;
+        res.y = m_top >= 0 ? res.y + sv.y : res.y;
+        res.z = m_top >= 0 ? res.z + sv.z : res.z;
+        res.w = m_top >= 0 ? res.w + sv.w : res.w;
+        res.x = gv.x > 0.f ? res.x : 0.f;
+        res.y = gv.y > 0.f ? res.y : 0.f;
+        res.z = gv.z > 0.f ? res.z : 0.f;
+        res.w = gv.w > 0.f ? res.w : 0.f;
+      } else if (a.self_add) {
+        // + the row's own term, stored row-compacted (row-uniform branch)
         const int32_t m = a.self_map[a.self_row0 + orow];
         if (m >= 0) {
           const float4 sv = *reinterpret_cast<const float4*>(a.self_add + m * a.ld_self + f);
@@ -235,7 +265,7 @@ __global__ __launch_bounds__(256) void spmm_f32_rowgroup_kernel(SpmmF32Args a) {
           res.w += sv.w;
         }
       }
-      if (a.gate) {  // ReLU derivative from a stored activation (row-uniform branch)
+      if (!GS && a.gate) {  // ReLU derivative from a stored activation (row-uniform branch)
         const float4 gv = *reinterpret_cast<const float4*>(a.gate + orow * a.ldgate + f);
         res.x = gv.x > 0.f ? res.x : 0.f;
         res.y = gv.y > 0.f ? res.y : 0.f;
@@ -297,7 +327,20 @@ hipError_t launch_f32_rg(const SpmmF32Args& a, hipStream_t st) {
     return hipErrorInvalidValue;
   }
   dim3 grid(static_cast<unsigned>(blocks)), block(256);
-#define DG_F32_K(LPR_, W_, C_, T_)                                                          \
+  // column-mapped pass with gate + self term and output rows in order (the input-layer
+  // gradient): the GS variant (self_add holds at least one row: the bindings drop an empty one)
+  if (cmap && wmode == 0 && a.gate && a.self_add && a.self_map && !a.row_map) {
+#define DG_F32_GS(LPR_, T_)                                                                    \
+    if (LPR == LPR_ && two == T_) {                                                            \
+      hipLaunchKernelGGL((spmm_f32_rowgroup_kernel<IdxT, LPR_, 0, true, T_, false, true>), grid, \
+                         block, 0, st, ka);                                                    \
+      return hipGetLastError();                                                                \
+    }
+    DG_F32_GS(8, false) DG_F32_GS(16, false) DG_F32_GS(32, false) DG_F32_GS(64, false)
+    DG_F32_GS(8, true) DG_F32_GS(16, true) DG_F32_GS(32, true) DG_F32_GS(64, true)
+#undef DG_F32_GS
+  }
+#define DG_F32_K(LPR_, W_, C_, T_)                                                         \
   if (LPR == LPR_ && wmode == W_ && cmap == C_ && two == T_) {                              \
     hipLaunchKernelGGL((spmm_f32_rowgroup_kernel<IdxT, LPR_, W_, C_, T_>), grid, block, 0, \
                        st, ka);                                                             \

@@ -24,7 +24,13 @@ backward, with S = T + N(T) (+ rows remote loss rows reach: the gradient support
 Exact: every term the dense backward has is computed (the omitted products are with rows
 that are zero by construction). Live device memory at the papers100M shape, W=1: x 57 GB +
 CSR 14 GB + h1 114 GB + h2 114 GB + ~4 GB of chunk buffers; dZ1 and u1 live in h2's
-storage after its last use. Kernels: fp32 row-group SpMM with row lists / column maps /
+storage after its last use. mean_N(x) is a constant of the graph and the features, and the
+plan has no room to keep it (53 GB), so B1b recomputes it per chunk — into the left d0
+columns of h1's rows of the same chunk, dead from there (their last reader, the chunk's
+gradient aggregation gated by h1, is already enqueued) until the next step's F0 writes
+them: that F0 reads its aggregate from there instead of aggregating (the chunk's GEMM
+reads its A rows before it stores its output rows, gemm_f32.hip), so a step aggregates x
+once, not twice, in no extra memory (``reuse_agg0``). Kernels: fp32 row-group SpMM with row lists / column maps /
 gates / two sources (csrc/kernels/spmm_f32.hip), MFMA f32 dual GEMM with
 bias/ReLU/gate/row-scatter epilogues (gemm_f32.hip), split-M MFMA weight gradients
 (wgrad_f32.hip), keep bits (bits.hip). Deterministic: fixed chunking, fixed reduction
@@ -74,6 +80,13 @@ from ..utils.config import ExecutorConfig
 # keep layer 0's input aggregate mean_N(x) from the forward for the backward when the
 # memory plan has room for it ("auto"), never ("off"), or require it ("on")
 #   -> ExecutorConfig.keep_agg0
+# 3 layers, no kept agg0, d0 <= hidden: the backward's recomputed mean_N(x) of a row chunk
+# goes into the left d0 columns of layer 0's (by then dead) output rows of that chunk, and
+# the NEXT step's layer 0 reads it from there instead of aggregating again ("auto"); "off":
+# recomputed into the chunk buffer and aggregated again by every forward. One full input
+# aggregation less per step from the second step on (papers100M W=1: PERFORMANCE.md).
+# Needs x and the graph unchanged between steps (invalidate_input_aggregate() otherwise)
+#   -> ExecutorConfig.reuse_agg0
 # W > 1, a forward layer whose exchange is in flight: after its interior rows, aggregate the
 # interior part of the boundary rows into a store before waiting ("on"), or wait and run the
 # boundary rows in one two-source pass ("off"); "auto" stores only when the modelled
@@ -338,6 +351,11 @@ class FusedSAGE:
     ``n_train``, so an all-reduce of the gradients gives the full-batch gradient).
     ``self.correct`` holds (validation hits, test hits) of the same forward.
 
+    The features ``x`` and the graph are taken as fixed for the life of the executor: with
+    ``reuse_agg0`` (``schedule["reuse_agg0"]``) a step's backward leaves ``mean_N(x)`` in
+    layer 0's output buffer for the next step's forward. A caller that changes either in
+    place calls :meth:`invalidate_input_aggregate` before the next ``step()``.
+
     ``release_graph=True``: the graph's interior / halo CSRs are dropped once this
     executor has built its own adjacency (DistGraph.release_csr) — the graph object is then
     only an exchange plan."""
@@ -394,6 +412,8 @@ class FusedSAGE:
         self.record = False
         self._events: list = []
         self._packs: dict = {}  # send-row packs in source order (_pack)
+        # h[0][:, :d0] holds mean_N(x) of every row (reuse_agg0; set by a finished backward)
+        self._agg0_in_h = False
         self._tune_passes()
 
     # ------------------------------------------------------------------ setup phases
@@ -593,6 +613,10 @@ class FusedSAGE:
             if take:
                 self.agg0 = torch.empty(L, self.d0, dtype=torch.float32, device=dev)
                 b.other += need0
+        # not kept: the backward's recomputed aggregate handed to the next forward through
+        # layer 0's output buffer (no memory of its own, so nothing to plan)
+        self.reuse_agg0 = (cfg.reuse_agg0 != "off" and self.nl == 3 and self.agg0 is None
+                           and self.d0 <= self.hid)
         # W > 1: the output layer's projection [L, Cp] (PROJECT_FIRST), after the kept
         # aggregates (those save whole aggregation passes)
         self.pf = None
@@ -1026,7 +1050,8 @@ class FusedSAGE:
                 "boundary_store": dict(self.use_store),
                 "halo_stream": ({"column_block": self.cw, "buffers": self.nbuf}
                                 if self.stream else False),
-                "keep_agg0": self.agg0 is not None, "keep_aS": self.aS_keep is not None,
+                "keep_agg0": self.agg0 is not None, "reuse_agg0": self.reuse_agg0,
+                "keep_aS": self.aS_keep is not None,
                 "output_self_term_fill": self.zself is not None,
                 "compact_T": self.TS is not None,
                 "compact_halo_T": self.HTS is not None, "compact_pull": self.PT is not None,
@@ -1036,6 +1061,13 @@ class FusedSAGE:
                 "memory_plan": list(self.memory_plan),
                 **({"link_gbps_planned": round(self.link_gbps, 1)}
                    if self.g.send_map is not None else {})}
+
+    def invalidate_input_aggregate(self) -> None:
+        """Forget the input aggregate ``mean_N(x)`` a previous step's backward left for the
+        next forward (``reuse_agg0``): the next ``step()`` aggregates ``x`` in its forward
+        again. To be called after ``x`` or the graph was changed in place; without such a
+        change both must stay fixed between steps."""
+        self._agg0_in_h = False
 
     # ------------------------------------------------------------------ helpers
     def _gemm(self, A1, B1, A2=None, B2=None, **kw):
@@ -1442,6 +1474,9 @@ class FusedSAGE:
         # ---------------- forward: hidden layers
         hin, hin_halo = x, (g._static_halo(x) if g.send_map is not None else None)
         halos = []
+        # the previous backward's mean_N(x) in h[0]'s left columns (cleared here: this
+        # forward overwrites those rows)
+        reuse0, self._agg0_in_h = self._agg0_in_h, False
         for l in range(nl - 1):
             ws, wn, b = P[l]
             if l == 0:
@@ -1489,6 +1524,13 @@ class FusedSAGE:
                         self._gemm(a, wn, cin=hout[r0:r1], beta=1.0, relu=True,
                                    out=hout[r0:r1])
                 halos.append(None)
+            elif l == 0 and reuse0:
+                # in place: a chunk's GEMM reads its aggregate rows (the left d0 columns
+                # of its own output rows) before it stores them
+                for ci, (r0, r1) in enumerate(self.chunks):
+                    if r1 > r0:
+                        consume(ci, hout[r0:r1, :self.d0])
+                halos.append(hin_halo)
             else:
                 # layer l >= 1 can store boundary-row aggregates in its own output buffer
                 store = hout[self.Li:] if (l > 0 and hin.shape[1] == hout.shape[1] and
@@ -1496,7 +1538,8 @@ class FusedSAGE:
                 keep = self.agg0 if l == 0 else None
                 halos.append(self._layer(hin, hin_halo, consume, hin.shape[1], f"fwd_l{l}",
                                          store=store, keep=keep))
-            self.edges_aggregated += nnz
+            if not (l == 0 and reuse0):
+                self.edges_aggregated += nnz
             hin = hout
             # this layer's halo rows leave now and land while the next layer works
             hin_halo = None if (self.stream or (self.pf is not None and l == nl - 2)) \
@@ -1821,19 +1864,25 @@ class FusedSAGE:
                 rp_s, rmap, _ = sr
                 self._spmm(rp_s, self.send_st.col, sg1, gz, beta=1.0, row_map=rmap,
                            gate=h1[r0:r1])
-            if self.agg0 is not None:
-                a0 = self.agg0[r0:r1]
-            else:
-                a0 = self._agg(x, r0, r1, self.bufA[:n, :self.d0], "all", x_halo)
             s0, s1 = self.ch_S[ci]
             if v is None and s1 > s0:  # no room for v_self: scattered self term
                 self._gemm(dZ[s0:s1], ws1_t, cin=gz, o_rows=self.ch_Sloc[ci],
                            gate=h1[r0:r1], out=gz)
+            if self.agg0 is not None:
+                a0 = self.agg0[r0:r1]
+            elif self.reuse_agg0:
+                # into the chunk's own rows of h1, left d0 columns: every reader of
+                # h1[r0:r1] of this step (the gates above) is enqueued, and the next
+                # forward's layer 0 finds its aggregate here
+                a0 = self._agg(x, r0, r1, h1[r0:r1, :self.d0], "all", x_halo)
+            else:
+                a0 = self._agg(x, r0, r1, self.bufA[:n, :self.d0], "all", x_halo)
             self.acc_in.add(x[r0:r1], gz, A2=a0)
         if not waited:
             self._mark("exchange_bwd_l0")
             work.wait()
             self._mark("bwd_l0")
+        self._agg0_in_h = self.reuse_agg0  # every chunk has written its slice
         db0 = self.acc_in.col_result()
         self.edges_aggregated += self.nnz_it + \
             (self.nnz_h if (uh is not None or full) else

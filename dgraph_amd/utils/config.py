@@ -75,6 +75,7 @@ class ExecutorConfig:
     chunk_rows: int = 0             # rows per chunk (0: from free memory)
     overlap: bool = True            # W>1: interior rows while the forward exchange flies
     keep_agg0: str = "auto"         # keep mean_N(x) for the backward: auto | on | off
+    reuse_agg0: str = "auto"        # backward's recomputed mean_N(x) feeds the next forward
     boundary_store: str = "auto"    # boundary rows' interior part pre-aggregated: auto|on|off
     keep_as: str = "auto"           # keep the S rows' last-hidden aggregate: auto|on|off
     stream_fill: bool = True        # streamed layers: self term during the first block
@@ -94,6 +95,7 @@ class ExecutorConfig:
 
     def __post_init__(self):
         for name, ok in (("keep_agg0", ("auto", "on", "off")),
+                         ("reuse_agg0", ("auto", "off")),
                          ("boundary_store", ("auto", "on", "off")),
                          ("keep_as", ("auto", "on", "off")),
                          ("halo_stream", ("auto", "on", "off")),
