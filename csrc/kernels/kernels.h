@@ -364,4 +364,35 @@ hipError_t gat_bwd_src_f32(IType it, const int64_t* rowptr, const void* col, int
                            const float* a_src, float* gz, int64_t ldgz, float* gss,
                            hipStream_t st);
 
+// ---------------------------------------------------------------------------
+// Fused fp32 scaled dot-product graph attention of one relation (dot_attn_f32.hip):
+// e_ij = scale <q_i, k_j> per head, softmax over each destination row's edges, the weighted
+// gather of v_j, and the exact adjoint (destination side: dq; source side over the
+// transposed pattern: dk and dv). Two sources: columns >= nsplit read k2 / v2. Every
+// feature array has its own row stride (floats); stat_m / stat_l / c share `lds`. A launch
+// needs row 0 of q and of the first gathered source to exist (padding slots read them).
+bool dot_attn_f32_shape_ok(int C, int heads);
+hipError_t dot_attn_fwd_f32(IType it, const int64_t* rowptr, const void* col, int64_t nrows,
+                            int C, int heads, int64_t lds, float scale, const float* q,
+                            int64_t ldq, const float* k, int64_t ldk, const float* v,
+                            int64_t ldv, const float* k2, int64_t ldk2, const float* v2,
+                            int64_t ldv2, int64_t nsplit, float* out, int64_t ldo, float beta,
+                            float* stat_m, float* stat_l, hipStream_t st);
+hipError_t dot_attn_bwd_dst_f32(IType it, const int64_t* rowptr, const void* col,
+                                int64_t nrows, int C, int heads, int64_t lds, float scale,
+                                const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                const float* v, int64_t ldv, const float* k2, int64_t ldk2,
+                                const float* v2, int64_t ldv2, int64_t nsplit,
+                                const float* stat_m, const float* stat_l, const float* g,
+                                int64_t ldg, const float* c, float* dq, int64_t lddq,
+                                hipStream_t st);
+// rows = source rows (k / v resident); col = destination ids (q, g, stat_m, stat_l, c rows)
+hipError_t dot_attn_bwd_src_f32(IType it, const int64_t* rowptr, const void* col,
+                                int64_t nrows, int C, int heads, int64_t lds, float scale,
+                                const float* q, int64_t ldq, const float* g, int64_t ldg,
+                                const float* k, int64_t ldk, const float* v, int64_t ldv,
+                                const float* stat_m, const float* stat_l, const float* c,
+                                float* dk, int64_t lddk, float* dv, int64_t lddv,
+                                hipStream_t st);
+
 }  // namespace dgraph

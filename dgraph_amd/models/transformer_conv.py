@@ -1,0 +1,85 @@
+"""Scaled dot-product graph attention layer (PyG's ``TransformerConv``, the UniMP layer) on
+a distributed relation.
+
+``CommAwareTransformerConv`` computes, for every destination vertex ``i`` of one relation and
+per head ``h`` (``out_channels = heads * D``, heads concatenated as in ``CommAwareGAT``)::
+
+    q_i = W_q x_i + b_q        [k_j | v_j] = W_kv x_j + b_kv
+    out_i[h] = sum_j softmax_j(<q_i[h], k_j[h]> / sqrt(D)) v_j[h]  (+ W_skip x_i) (+ bias)
+
+MI355X formulation (with a :class:`~dgraph_amd.data.hetero.RelationGraph`):
+
+* keys and values come from ONE GEMM into one ``[N, 2C]`` buffer; the attention kernels read
+  its two column halves in place (row stride ``2C``);
+* with more than one rank, ONE halo exchange moves the ``[k | v]`` rows of remote sources
+  (:class:`~dgraph_amd.parallel.halo.HaloExchange`; its adjoint returns their gradient in
+  backward), issued on every rank whether or not it receives rows; the received rows are
+  read as a second source, never concatenated with the local ones;
+* the attention itself is :func:`~dgraph_amd.ops.dot_attn.dot_attention`: three fused
+  kernels, no per-edge tensor (GPU fp32), or its fp64 plain-PyTorch evaluation (CPU).
+
+Out of scope here: wiring the layer into ``CommAwareRGAT``, the lean ``HeteroGraph`` path or
+the OGB-LSC trainer; bf16; edge features; PyG's ``beta`` gate between the skip and the
+attention output; attention dropout.
+"""
+from __future__ import annotations
+
+import torch
+import torch.nn as nn
+
+from ..ops.dot_attn import dot_attention
+from ..ops.gat import GatPattern
+from .rgat import _world
+
+
+class CommAwareTransformerConv(nn.Module):
+    def __init__(self, in_channels: int, out_channels: int, comm=None, heads: int = 1,
+                 bias: bool = True, root_weight: bool = True, hetero: bool = False):
+        super().__init__()
+        if out_channels % heads:
+            raise ValueError("out_channels must be divisible by heads")
+        self.comm = comm
+        self.heads = heads
+        self.hetero = hetero
+        self.out_channels = out_channels
+        self.lin_query = nn.Linear(in_channels, out_channels)
+        self.lin_kv = nn.Linear(in_channels, 2 * out_channels)  # rows [W_k ; W_v]
+        if root_weight:
+            self.lin_skip = nn.Linear(in_channels, out_channels, bias=False)
+        else:
+            self.register_module("lin_skip", None)
+        if bias:
+            self.bias = nn.Parameter(torch.zeros(out_channels))
+        else:
+            self.register_parameter("bias", None)
+        self._halo = None
+
+    @staticmethod
+    def _pattern(graph) -> GatPattern:
+        """The relation's attention pattern and its transpose, built once per graph."""
+        pat = graph._cache.get("dot_attn_pattern")
+        if pat is None:
+            pat = GatPattern(graph.csr.rowptr, graph.csr.col, graph.num_local_src,
+                             graph.num_halo)
+            graph._cache["dot_attn_pattern"] = pat
+        return pat
+
+    def forward(self, x, graph, x_j=None):
+        C = self.out_channels
+        q = self.lin_query(x)
+        kv = self.lin_kv(x_j if (self.hetero and x_j is not None) else x)
+        kh = vh = None
+        if _world(self.comm) > 1:  # collective on every rank of the relation's group
+            from ..parallel.halo import HaloExchange
+
+            if self._halo is None:
+                self._halo = HaloExchange(self.comm)
+            halo = self._halo(kv, graph.pattern)
+            kh, vh = halo[:, :C], halo[:, C:]
+        out = dot_attention(q, kv[:, :C], kv[:, C:], self._pattern(graph), kh, vh,
+                            heads=self.heads)
+        if self.lin_skip is not None:
+            out = out + self.lin_skip(x)
+        if self.bias is not None:
+            out = out + self.bias
+        return out

@@ -1,0 +1,7 @@
+def __getattr__(name):
+    # ``from dgraph_amd.ops import dot_attention`` (imported on first use: the op modules
+    # import each other and the native loader)
+    if name == "dot_attention":
+        from .dot_attn import dot_attention
+        return dot_attention
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
