@@ -140,6 +140,48 @@ hipError_t segment_extreme_bwd(DType dt, IType it, const int64_t* t_rowptr, cons
                                hipStream_t stream);
 
 // ---------------------------------------------------------------------------
+// Fused neighbourhood statistics for PNA (spmm_pna.hip), fp32: mean, standard deviation,
+// max and min of the same neighbour rows in ONE gather pass. For CSR row r (output row
+// row_map[r] when given) with n = max(total entry count, 1):
+//   mean[r, f] = sum_k x[col[k], f] / n
+//   sdev[r, f] = sqrt(max(sum_k (x[col[k], f] - mean[r, f])^2, 0) / n + eps)
+//   vmax / amax, vmin / amin: exactly segment_extreme_fwd (first slot wins, 0 / -1 for an
+//   empty row).
+// The pair (mean, sdev), the pair (vmax, amax) and the pair (vmin, amin) are each optional
+// (both pointers null: nothing stored); every array has its own row stride, unit column
+// stride. The variance is summed about a pivot per lane group and the groups are merged
+// pairwise (Chan), never as E[x^2] - E[x]^2; fixed order => bitwise reproducible.
+// Two sources: the first pass runs with final = false and leaves mean = its mean, sdev =
+// its sum of squared deviations M2. The second pass (second = true, final = true) merges
+// its own (n_b, mean_b, M2_b) with that incumbent, whose count is
+// prev_rowptr[o + 1] - prev_rowptr[o] for output row o, and finalises; extremes follow the
+// second-source rule of segment_extreme_fwd (-2 - offset). It finalises only the rows it
+// visits, so it must be run over ALL output rows (the uncompacted second block).
+// Backward over the transposed pattern (row c = source row of x, t_col = destination rows,
+// rel as in segment_extreme_bwd, inv_deg[r] = 1 / n of destination r):
+//   out[c, f] = beta * out[c, f] + sum_k inv_deg[r] * (g_mean[r, f] + g_std[r, f] *
+//               (x[c, f] - mean[r, f]) / sdev[r, f])
+//               + g_max[r, f] * [amax[r, f] == key_k] + g_min[r, f] * [amin[r, f] == key_k]
+// with r = t_col[k], key_k = rel[k] (halo: -2 - rel[k]). Null g_* drop their terms.
+// ---------------------------------------------------------------------------
+hipError_t segment_pna_fwd(IType it, const int64_t* rowptr, const void* col, const float* x,
+                           int64_t ldx, float* mean, int64_t ld_mean, float* sdev,
+                           int64_t ld_sdev, float* vmax, int64_t ld_vmax, int32_t* amax,
+                           int64_t ld_amax, float* vmin, int64_t ld_vmin, int32_t* amin,
+                           int64_t ld_amin, int64_t nrows, int F, float eps, bool second,
+                           bool final, const int64_t* prev_rowptr, const int64_t* row_map,
+                           hipStream_t stream);
+hipError_t segment_pna_bwd(IType it, const int64_t* t_rowptr, const void* t_col,
+                           const int32_t* rel, const float* x, int64_t ldx,
+                           const float* inv_deg, const float* g_mean, int64_t ld_gmean,
+                           const float* g_std, int64_t ld_gstd, const float* mean,
+                           int64_t ld_mean, const float* sdev, int64_t ld_sdev,
+                           const float* g_max, int64_t ld_gmax, const int32_t* amax,
+                           int64_t ld_amax, const float* g_min, int64_t ld_gmin,
+                           const int32_t* amin, int64_t ld_amin, float* out, int64_t ldo,
+                           int64_t nrows, int F, bool halo, float beta, hipStream_t stream);
+
+// ---------------------------------------------------------------------------
 // Row copy with optional source and destination index (K4/K7/K8 replacement, K-new-1).
 //   out[dst(i)] (+)= x[src(i)]   for i in [0, n)
 // src/dst null == identity. src(i) < 0 writes zeros; dst(i) < 0 skips the row.

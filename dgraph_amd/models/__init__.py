@@ -1,0 +1,7 @@
+def __getattr__(name):
+    # ``from dgraph_amd.models import CommAwarePNAConv`` (imported on first use: the model
+    # modules import the op library and the native loader)
+    if name == "CommAwarePNAConv":
+        from .pna import CommAwarePNAConv
+        return CommAwarePNAConv
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -2,6 +2,8 @@
 
 * :func:`aggregate` — CSR SpMM (sum / mean / edge-weighted, multi-head); backward is the
   same kernel on the cached transposed CSR (or on the same CSR for symmetric patterns).
+* :func:`aggregate_multi` — mean, max, min and standard deviation of the same neighbour
+  rows in ONE gather pass (the PNA aggregators), as column blocks of one ``[R, A*F]`` tensor.
 * :func:`gather` / :func:`scatter_sum` — vertex->edge gather and edge->vertex scatter-sum
   over a static :class:`~dgraph_amd.ops.csr.IndexMap`; each is the other's adjoint
   (the core contract of the reference, tests/test_NCCLCommPlan.py:100-111,297-307),
@@ -79,6 +81,92 @@ class _AggregateExtremeFn(Function):
         return K.segment_extreme_bwd(t.rowptr, t.col, rel, g.contiguous(), arg), None, None
 
 
+PNA_AGGREGATORS = ("mean", "max", "min", "std")
+
+
+def check_aggregators(aggregators) -> tuple:
+    """``aggregators`` as a tuple of distinct names out of :data:`PNA_AGGREGATORS`."""
+    aggs = (aggregators,) if isinstance(aggregators, str) else tuple(aggregators)
+    bad = [a for a in aggs if a not in PNA_AGGREGATORS]
+    if bad or not aggs or len(set(aggs)) != len(aggs):
+        raise ValueError(f"aggregators must be distinct names out of {PNA_AGGREGATORS}, "
+                         f"got {aggs!r}")
+    return aggs
+
+
+def multi_blocks(buf: torch.Tensor, aggregators: tuple, F: int) -> dict:
+    """The column blocks of a ``[R, A*F]`` buffer by aggregator name (views)."""
+    return {a: buf[:, i * F:(i + 1) * F] for i, a in enumerate(aggregators)}
+
+
+def vec_rows(x: torch.Tensor) -> torch.Tensor:
+    """``x`` as the fused kernels take a row array: unit column stride, and on the GPU, for
+    a width that is a multiple of 4, a row stride divisible by 4 and a 16-B aligned base
+    (a copy only when the view is not)."""
+    F = x.shape[1]
+    if x.stride(1) != 1 and F > 1:
+        return x.contiguous()
+    if x.is_cuda and F % 4 == 0 and x.shape[0] > 1 and (
+            x.stride(0) % 4 or x.data_ptr() % (4 * x.element_size())):
+        return x.contiguous()
+    return x
+
+
+class _AggregateMultiFn(Function):
+    """The PNA aggregators of each row's entries from one pass over the neighbour rows
+    (K.segment_pna); the backward is one gather over the transposed pattern."""
+
+    @staticmethod
+    def forward(ctx, x, csr: CSR, aggregators: tuple, eps: float):
+        R, F = csr.num_rows, x.shape[1]
+        out = torch.empty(R, len(aggregators) * F, dtype=x.dtype, device=x.device)
+        blk = multi_blocks(out, aggregators, F)
+        mean, sdev = blk.get("mean"), blk.get("std")
+        if mean is not None or sdev is not None:  # the moments come as a pair
+            mean = torch.empty(R, F, dtype=x.dtype, device=x.device) if mean is None else mean
+            sdev = torch.empty(R, F, dtype=x.dtype, device=x.device) if sdev is None else sdev
+        args = {k: torch.empty(R, F, dtype=torch.int32, device=x.device)
+                for k in ("max", "min") if k in blk}
+        K.segment_pna(csr.rowptr, csr.col, x, mean=mean, sdev=sdev, vmax=blk.get("max"),
+                      amax=args.get("max"), vmin=blk.get("min"), amin=args.get("min"), eps=eps)
+        ctx.csr, ctx.aggregators = csr, aggregators
+        # the moments that are blocks of ``out`` are saved with it, the others on their own
+        ctx.save_for_backward(x, out, None if "mean" in blk else mean,
+                              None if "std" in blk else sdev, args.get("max"), args.get("min"))
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, out, mean, sdev, amax, amin = ctx.saved_tensors
+        csr: CSR = ctx.csr
+        blk = multi_blocks(out.detach(), ctx.aggregators, x.shape[1])
+        mean, sdev = blk.get("mean", mean), blk.get("std", sdev)
+        gb = multi_blocks(g.contiguous(), ctx.aggregators, x.shape[1])
+        t, rel = csr.transpose_rel()
+        inv = csr.inv_degree()
+        if x.dtype == torch.float64:
+            inv = 1.0 / csr.degree().clamp(min=1).double()
+        gx = K.segment_pna_bwd(t.rowptr, t.col, rel, x, inv, g_mean=gb.get("mean"),
+                               g_std=gb.get("std"), mean=mean, sdev=sdev, g_max=gb.get("max"),
+                               amax=amax, g_min=gb.get("min"), amin=amin)
+        return gx, None, None, None
+
+
+def aggregate_multi(x: torch.Tensor, csr: CSR, aggregators=PNA_AGGREGATORS,
+                    eps: float = 1e-5) -> torch.Tensor:
+    """Several aggregations of the same neighbour rows at once: ``[R, A*F]``, one ``F``-wide
+    column block per name in ``aggregators`` (any distinct subset of ``"mean"``, ``"max"``,
+    ``"min"``, ``"std"``, in the order given), so the result feeds one GEMM without a
+    ``cat``. ``mean`` / ``max`` / ``min`` are :func:`aggregate`'s; ``std`` is the population
+    standard deviation ``sqrt(mean((x_j - mean)^2) + eps)`` (``sqrt(eps)`` for an empty row,
+    PyG's value). On the GPU (fp32) one kernel gathers each neighbour row once for all of
+    them, and one kernel computes the gradient."""
+    aggs = check_aggregators(aggregators)
+    if aggs == ("mean",):
+        return aggregate(x, csr, reduce="mean")
+    return _AggregateMultiFn.apply(vec_rows(x), csr, aggs, float(eps))
+
+
 def aggregate(
     x: torch.Tensor,
     csr: CSR,
@@ -94,7 +182,17 @@ def aggregate(
     ``reduce="max"`` / ``"min"``: the elementwise extremum over a row's entries (0 for an
     empty row), unweighted and single-head. Its gradient goes to ONE entry per
     ``(row, feature)``: the first in CSR slot order that attains the extremum.
+
+    ``reduce="std"``: the population standard deviation over a row's entries,
+    ``sqrt(mean((x_j - mean)^2) + 1e-5)``, unweighted and single-head: the ``"std"`` block of
+    :func:`aggregate_multi`, which computes several of these from one pass.
     """
+    if reduce == "std":
+        if edge_weight is not None:
+            raise ValueError("reduce='std' takes no edge weights")
+        if heads != 1:
+            raise ValueError(f"reduce='std' takes one head, got heads={heads}")
+        return aggregate_multi(x, csr, ("std",))
     if reduce in ("max", "min"):
         if edge_weight is not None:
             raise ValueError(f"reduce={reduce!r} takes no edge weights")

@@ -151,6 +151,89 @@ def segment_extreme_bwd(
     return _ref.segment_extreme_bwd(t_rowptr, t_col, rel, g, arg, out, halo, beta)
 
 
+def segment_pna(
+    rowptr: torch.Tensor,
+    col: torch.Tensor,
+    x: torch.Tensor,
+    *,
+    mean: Optional[torch.Tensor] = None,
+    sdev: Optional[torch.Tensor] = None,
+    vmax: Optional[torch.Tensor] = None,
+    amax: Optional[torch.Tensor] = None,
+    vmin: Optional[torch.Tensor] = None,
+    amin: Optional[torch.Tensor] = None,
+    eps: float = 1e-5,
+    second: bool = False,
+    final: bool = True,
+    prev_rowptr: Optional[torch.Tensor] = None,
+    row_map: Optional[torch.Tensor] = None,
+) -> None:
+    """Mean, standard deviation, max and min of each CSR row's entries in ONE pass over the
+    neighbour rows, written into the given outputs (each ``[rows, F]`` with its own row
+    stride: normally the column blocks of one ``[rows, A*F]`` buffer). With
+    ``n = max(entries, 1)``: ``mean = sum x / n``,
+    ``sdev = sqrt(max(sum (x - mean)^2, 0) / n + eps)`` (an empty row: 0 and ``sqrt(eps)``);
+    ``vmax`` / ``amax`` and ``vmin`` / ``amin`` exactly as :func:`segment_extreme`. The three
+    pairs are each optional.
+
+    Two sources: the first pass runs with ``final=False`` (``sdev`` then holds the sum of
+    squared deviations), the second with ``second=True`` and ``prev_rowptr`` = the first
+    source's row pointer over the OUTPUT rows; it must visit every output row (no
+    row-compacted block), since a pass finalises only the rows it visits. ``row_map`` as in
+    :func:`spmm`."""
+    if (mean is None) != (sdev is None) or (vmax is None) != (amax is None) \
+            or (vmin is None) != (amin is None):
+        raise ValueError("segment_pna: (mean, sdev), (vmax, amax), (vmin, amin) come in pairs")
+    if second and mean is not None and prev_rowptr is None:
+        raise ValueError("segment_pna: a second pass over the moments needs prev_rowptr")
+    if _native_ok(x):
+        _native.ops().segment_pna_fwd(rowptr, col, x, mean, sdev, vmax, amax, vmin, amin,
+                                      float(eps), bool(second), bool(final), prev_rowptr,
+                                      row_map)
+        return
+    _ref.segment_pna(rowptr, col, x, mean, sdev, vmax, amax, vmin, amin, eps, second, final,
+                     prev_rowptr, row_map)
+
+
+def segment_pna_bwd(
+    t_rowptr: torch.Tensor,
+    t_col: torch.Tensor,
+    rel: torch.Tensor,
+    x: torch.Tensor,
+    inv_deg: Optional[torch.Tensor],
+    out: Optional[torch.Tensor] = None,
+    *,
+    g_mean: Optional[torch.Tensor] = None,
+    g_std: Optional[torch.Tensor] = None,
+    mean: Optional[torch.Tensor] = None,
+    sdev: Optional[torch.Tensor] = None,
+    g_max: Optional[torch.Tensor] = None,
+    amax: Optional[torch.Tensor] = None,
+    g_min: Optional[torch.Tensor] = None,
+    amin: Optional[torch.Tensor] = None,
+    halo: bool = False,
+    beta: float = 0.0,
+) -> torch.Tensor:
+    """Backward of :func:`segment_pna` as a gather over the transposed pattern (the triple
+    of :func:`segment_extreme_bwd`); ``x`` holds this block's source rows, ``inv_deg[r]`` is
+    ``1 / max(total entries of destination r, 1)``:
+    ``out[c] = beta * out[c] + sum_k inv_deg[r] (g_mean[r] + g_std[r] (x[c] - mean[r]) /
+    sdev[r]) + g_max[r] [amax[r] == key_k] + g_min[r] [amin[r] == key_k]``, ``r = t_col[k]``,
+    ``key_k = rel[k]`` (``halo``: ``-2 - rel[k]``). ``None`` gradients drop their terms. No
+    atomics; fixed summation order."""
+    C = t_rowptr.numel() - 1
+    if out is None:
+        out = torch.empty(C, x.shape[1], dtype=x.dtype, device=x.device)
+        beta = 0.0
+    if _native_ok(x):
+        _native.ops().segment_pna_bwd(t_rowptr, t_col, rel, x, inv_deg, g_mean, g_std, mean,
+                                      sdev, g_max, amax, g_min, amin, out, bool(halo),
+                                      float(beta))
+        return out
+    return _ref.segment_pna_bwd(t_rowptr, t_col, rel, x, inv_deg, out, g_mean, g_std, mean,
+                                sdev, g_max, amax, g_min, amin, halo, beta)
+
+
 def copy_rows(
     x: torch.Tensor,
     src_idx: Optional[torch.Tensor] = None,

@@ -162,6 +162,85 @@ def segment_extreme_bwd(t_rowptr, t_col, rel, g, arg, out, halo=False, beta=0.0)
     return out
 
 
+def segment_pna(rowptr, col, x, mean=None, sdev=None, vmax=None, amax=None, vmin=None,
+                amin=None, eps=1e-5, second=False, final=True, prev_rowptr=None, row_map=None):
+    """Fused mean / standard deviation / max / min of each CSR row's entries (cf. kernels.h),
+    evaluated in two passes: the mean first, then the squared deviations about it. With
+    ``n = max(entries of the row over all sources, 1)``: ``mean = sum x / n``,
+    ``sdev = sqrt(max(sum (x - mean)^2, 0) / n + eps)``; the extremes are
+    :func:`segment_extreme`. The pairs ``(mean, sdev)``, ``(vmax, amax)``, ``(vmin, amin)``
+    are each optional. ``final=False`` leaves ``sdev`` = the sum of squared deviations M2;
+    ``second``: the outputs hold such an incumbent of ``prev_rowptr``'s row counts, which
+    this pass merges with its own ``(n, mean, M2)`` (the pairwise formula) and, with
+    ``final``, finalises. fp32 (fp64 for fp64 input)."""
+    R = rowptr.numel() - 1
+    F = x.shape[1]
+    if R <= 0 or F == 0:
+        return
+    for out, arg, minimum in ((vmax, amax, False), (vmin, amin, True)):
+        if out is not None:
+            segment_extreme(rowptr, col, x, out, arg, minimum, second, row_map)
+    if mean is None:
+        return
+    cdt = torch.float64 if x.dtype == torch.float64 else torch.float32
+    rows = _row_ids(rowptr)
+    vals = x.to(cdt)[col.long()]
+    nb = (rowptr[1:] - rowptr[:-1]).to(cdt).unsqueeze(1)
+    mb = torch.zeros(R, F, dtype=cdt, device=x.device).index_add_(0, rows, vals)
+    mb = mb / nb.clamp(min=1)
+    qb = torch.zeros(R, F, dtype=cdt, device=x.device).index_add_(
+        0, rows, (vals - mb[rows]).square())
+    tgt = slice(0, R) if row_map is None else row_map.long()
+    n = nb
+    if second:
+        na = (prev_rowptr[1:] - prev_rowptr[:-1])[tgt].to(cdt).unsqueeze(1)
+        ma, qa = mean[tgt].to(cdt), sdev[tgt].to(cdt)
+        n = na + nb
+        w = nb / n.clamp(min=1)
+        dl = mb - ma
+        mb = ma + dl * w
+        qb = qa + qb + dl * dl * (na * w)
+    if final:
+        qb = (qb.clamp(min=0) / n.clamp(min=1) + eps).sqrt()
+    mean[tgt] = mb.to(mean.dtype)
+    sdev[tgt] = qb.to(sdev.dtype)
+
+
+def segment_pna_bwd(t_rowptr, t_col, rel, x, inv_deg, out, g_mean=None, g_std=None, mean=None,
+                    sdev=None, g_max=None, amax=None, g_min=None, amin=None, halo=False,
+                    beta=0.0):
+    """Backward of :func:`segment_pna` over the transposed pattern (cf. kernels.h): source
+    row ``c`` sums, over its entries ``(r = t_col[k], rel[k])``,
+    ``inv_deg[r] (g_mean[r] + g_std[r] (x[c] - mean[r]) / sdev[r])`` and the ``g_max`` /
+    ``g_min`` of the destinations whose ``amax`` / ``amin`` name the entry. ``None``
+    gradients drop their terms. fp32 accumulate (fp64 for fp64)."""
+    C = t_rowptr.numel() - 1
+    F = out.shape[1]
+    if C <= 0 or F == 0:
+        return out
+    cdt = torch.float64 if out.dtype == torch.float64 else torch.float32
+    src = _row_ids(t_rowptr)
+    r = t_col.long()
+    key = ((-2 - rel.long()) if halo else rel.long()).unsqueeze(1)
+    term = torch.zeros(r.numel(), F, dtype=cdt, device=out.device)
+    if g_mean is not None or g_std is not None:
+        b = torch.zeros_like(term)
+        if g_mean is not None:
+            b = b + g_mean.to(cdt)[r]
+        if g_std is not None:
+            b = b + g_std.to(cdt)[r] * ((x.to(cdt)[src] - mean.to(cdt)[r]) / sdev.to(cdt)[r])
+        term = inv_deg.to(cdt)[r].unsqueeze(1) * b
+    zero = torch.zeros((), dtype=cdt)
+    for g, arg in ((g_max, amax), (g_min, amin)):
+        if g is not None:
+            term = term + torch.where(arg[r].long() == key, g.to(cdt)[r], zero)
+    acc = torch.zeros(C, F, dtype=cdt, device=out.device).index_add_(0, src, term)
+    if beta != 0.0:
+        acc = acc + beta * out[:C].to(cdt)
+    out[:C] = acc.to(out.dtype)
+    return out
+
+
 def copy_rows(
     x: torch.Tensor,
     src_idx: Optional[torch.Tensor],

@@ -25,6 +25,7 @@ from torch.autograd import Function
 
 from ..comm.alltoallv import AllToAllV
 from ..ops import kernels as K
+from ..ops.aggregate import check_aggregators, multi_blocks, vec_rows
 from ..ops.csr import CSR, IndexMap
 
 
@@ -456,6 +457,117 @@ class DistGraph:
             K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
         return out
 
+    def degree(self) -> torch.Tensor:
+        """Total in-degree of every local vertex (interior + halo entries), int64."""
+        deg = self.interior.degree()
+        return deg + self.halo.degree() if self.halo is not None else deg
+
+    def _inv_deg_as(self, dtype) -> torch.Tensor:
+        if dtype == torch.float64:  # the CPU reference at full precision
+            return 1.0 / self.degree().clamp(min=1).double()
+        return self.inv_deg
+
+    def aggregate_multi(self, x: torch.Tensor, aggregators=("mean", "max", "min", "std"),
+                        eps: float = 1e-5, halo_rows: Optional[torch.Tensor] = None):
+        """Mean / max / min / standard deviation over in-neighbours, local and halo, from
+        ONE pass per block over the neighbour rows (:func:`~dgraph_amd.ops.kernels.
+        segment_pna`), on the schedule of :meth:`aggregate_extreme`: the interior pass runs
+        (non-final) while the halo rows are on the links, then the halo block is merged in
+        as a second source over all ``L`` rows, which finalises them. Returns ``(out,
+        saved)``: ``out`` is ``[L, A*F]``, one column block per name in ``aggregators``;
+        ``saved`` is what :meth:`aggregate_multi_T` needs (``mean``, ``sdev``, ``amax``,
+        ``amin`` and ``halo``, the halo rows this pass read: the std term of the gradient
+        needs ``x`` of the halo sources). ``halo_rows`` as in :meth:`aggregate`."""
+        aggs = check_aggregators(aggregators)
+        self.edges_aggregated += self.nnz
+        L, F = self.L, x.shape[1]
+        it = self.interior
+        new = lambda dt: torch.empty(L, F, dtype=dt, device=x.device)  # noqa: E731
+        out = torch.empty(L, len(aggs) * F, dtype=x.dtype, device=x.device)
+        blk = multi_blocks(out, aggs, F)
+        o = dict(mean=blk.get("mean"), sdev=blk.get("std"), vmax=blk.get("max"),
+                 vmin=blk.get("min"), amax=None, amin=None)
+        if o["mean"] is not None or o["sdev"] is not None:
+            o["mean"] = new(x.dtype) if o["mean"] is None else o["mean"]
+            o["sdev"] = new(x.dtype) if o["sdev"] is None else o["sdev"]
+        if o["vmax"] is not None:
+            o["amax"] = new(torch.int32)
+        if o["vmin"] is not None:
+            o["amin"] = new(torch.int32)
+        saved = dict(mean=o["mean"], sdev=o["sdev"], amax=o["amax"], amin=o["amin"], halo=None)
+        # a halo block with no entry (a rank that only sends) changes nothing: the interior
+        # pass is then final; the exchanges are posted all the same
+        two = self.halo is not None and self.halo.nnz > 0
+        if self.halo is None or halo_rows is not None:
+            K.segment_pna(it.rowptr, it.col, x, eps=eps, final=not two, **o)
+            if two:
+                K.segment_pna(self.halo.rowptr, self.halo.col, halo_rows, eps=eps, second=True,
+                              prev_rowptr=it.rowptr, **o)
+            saved["halo"] = halo_rows
+            return out, saved
+        pend = []
+        for c0, c1 in self._col_chunks(self.a2a, F, x.element_size()):
+            xc = x if (c0, c1) == (0, F) else x[:, c0:c1]
+            recv, work = self.a2a(K.gather_rows(xc, self.send_map.idx), async_op=True)
+            if not self.overlap:
+                work.wait()
+            pend.append((c0, c1, recv, work))
+        K.segment_pna(it.rowptr, it.col, x, eps=eps, final=not two, **o)
+        for c0, c1, recv, work in pend:
+            work.wait()
+            if two:
+                oc = o if (c0, c1) == (0, F) else \
+                    {k: None if v is None else v[:, c0:c1] for k, v in o.items()}
+                K.segment_pna(self.halo.rowptr, self.halo.col, recv, eps=eps, second=True,
+                              prev_rowptr=it.rowptr, **oc)
+        saved["halo"] = pend[0][2] if len(pend) == 1 else torch.cat([p[2] for p in pend], 1)
+        return out, saved
+
+    def aggregate_multi_T(self, g: torch.Tensor, x: torch.Tensor, saved: dict,
+                          aggregators=("mean", "max", "min", "std"),
+                          out: Optional[torch.Tensor] = None,
+                          halo_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Backward of :meth:`aggregate_multi` (``g``: ``[L, A*F]``, ``x`` and ``saved``:
+        the forward's input and second result). The moments' gradient and the interior
+        winners are gathered over the interior's transposed pattern with ``x``, the halo
+        block's over its transposed pattern with the kept halo rows into ``[H, F]`` rows,
+        which then take the reverse path of :meth:`aggregate_extreme_T` (reverse exchange,
+        owner-side segment sum). ``halo_out``: ``[H, F]`` buffer that keeps the halo
+        gradient here."""
+        aggs = check_aggregators(aggregators)
+        F = x.shape[1]
+        gb = multi_blocks(g.contiguous(), aggs, F)
+        it, irel = self.interior.transpose_rel()
+        self.edges_aggregated += it.nnz + (self.halo.nnz if self.halo is not None else 0)
+        inv = self._inv_deg_as(x.dtype)
+        kw = dict(g_mean=gb.get("mean"), g_std=gb.get("std"), mean=saved["mean"],
+                  sdev=saved["sdev"], g_max=gb.get("max"), amax=saved["amax"],
+                  g_min=gb.get("min"), amin=saved["amin"])
+        if self.halo is None:
+            return K.segment_pna_bwd(it.rowptr, it.col, irel, x, inv, out, **kw)
+        ht, hrel = self.halo.transpose_rel()
+        xh = saved["halo"]
+        if halo_out is not None:
+            K.segment_pna_bwd(ht.rowptr, ht.col, hrel, xh, inv, halo_out, halo=True, **kw)
+            return K.segment_pna_bwd(it.rowptr, it.col, irel, x, inv, out, **kw)
+        pend = []
+        for c0, c1 in self._col_chunks(self.a2a_rev, F, g.element_size()):
+            whole = (c0, c1) == (0, F)
+            kc = kw if whole else {k: None if v is None else v[:, c0:c1] for k, v in kw.items()}
+            hg = K.segment_pna_bwd(ht.rowptr, ht.col, hrel, xh if whole else xh[:, c0:c1], inv,
+                                   halo=True, **kc)
+            sg, work = self.a2a_rev(hg, async_op=True)
+            if not self.overlap:
+                work.wait()
+            pend.append((c0, c1, sg, work))
+        out = K.segment_pna_bwd(it.rowptr, it.col, irel, x, inv, out, **kw)
+        st = self.send_map.transpose_csr().compact_rows()
+        for c0, c1, sg, work in pend:
+            work.wait()
+            oc = out if (c0, c1) == (0, F) else out[:, c0:c1]
+            K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
+        return out
+
     def _peers(self) -> bool:
         """True when the plan's peers exist (a process group of the plan's size)."""
         import torch.distributed as dist
@@ -680,6 +792,37 @@ class _DistAggregateExtremeFn(Function):
     def backward(ctx, g):
         (arg,) = ctx.saved_tensors
         return ctx.graph.aggregate_extreme_T(g, arg), None, None
+
+
+class _DistAggregateMultiFn(Function):
+    @staticmethod
+    def forward(ctx, x, graph: DistGraph, aggregators: tuple, eps: float):
+        x = vec_rows(x)
+        out, saved = graph.aggregate_multi(x, aggregators, eps)
+        ctx.graph, ctx.aggregators = graph, aggregators
+        # the moments that are blocks of ``out`` are saved with it, the others on their own
+        ctx.save_for_backward(x, out, None if "mean" in aggregators else saved["mean"],
+                              None if "std" in aggregators else saved["sdev"], saved["amax"],
+                              saved["amin"], saved["halo"])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, out, mean, sdev, amax, amin, halo = ctx.saved_tensors
+        blk = multi_blocks(out.detach(), ctx.aggregators, x.shape[1])
+        saved = dict(mean=blk.get("mean", mean), sdev=blk.get("std", sdev), amax=amax,
+                     amin=amin, halo=halo)
+        return ctx.graph.aggregate_multi_T(g, x, saved, ctx.aggregators), None, None, None
+
+
+def dist_aggregate_multi(x: torch.Tensor, graph: DistGraph,
+                         aggregators=("mean", "max", "min", "std"),
+                         eps: float = 1e-5) -> torch.Tensor:
+    """Autograd-aware distributed :func:`~dgraph_amd.ops.aggregate.aggregate_multi`: the
+    aggregations named in ``aggregators`` of every local vertex's in-neighbours, local and
+    halo, as the column blocks of one ``[L, A*F]`` tensor (one exchange forward, one
+    backward; :meth:`DistGraph.aggregate_multi`)."""
+    return _DistAggregateMultiFn.apply(x, graph, check_aggregators(aggregators), float(eps))
 
 
 def dist_aggregate(x: torch.Tensor, graph: DistGraph, mean: bool = True,
