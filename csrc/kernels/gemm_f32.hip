@@ -24,6 +24,12 @@
 //     against B-fragment reads pinned a whole MFMA step ahead, and against the next stage's
 //     fragments prefetched behind the last MFMA step: all within +-0.3 % on the papers100M
 //     step (profiles/r04/gemm_f32_staging_ab.log), so the simplest form is kept;
+//   * the stage loop carries no address arithmetic: a lane's four A source pointers are built
+//     once per operand of a tile and advance by 32 floats per stage, a B row is a scalar
+//     base plus the lane's 16 B (glds16_sbase_to), and the stage's 8 DMAs go out behind its
+//     first four MFMA steps, one A piece and one B row each, instead of as a burst with
+//     ~150 VALU ahead of the first MFMA, during which both waves of a SIMD left the matrix
+//     pipe idle (PERFORMANCE.md round 8: -2.4 to -3.3 % per call, bitwise the same sums);
 //   * k order inside a stage: lane group h = lane>>4 takes k = 8h + j in MFMA step j, so a
 //     lane's A fragments of the stage are two 16-B pieces (2 x ds_read_b128) and its B
 //     fragment of step j is row 8h + j (the permutation is applied to A and B alike; the
@@ -128,7 +134,7 @@ __device__ __forceinline__ void gemm_f32_body(
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int tid = threadIdx.x;
   const int lane = tid & 63;
-  const int wave = tid >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // scalar: staging bases below
   const int wm = wave / WN, wn = wave % WN;
   const int li = lane & 15;  // fragment row (A) / column (B, C)
   const int lh = lane >> 4;  // k slot group
@@ -157,12 +163,20 @@ __device__ __forceinline__ void gemm_f32_body(
   // l%8 of the row, which holds global chunk (l%8) ^ swz(row): the A swizzle moved to the
   // per-lane SOURCE address) and 4 B rows (row kr = 4w + u, lane l < N/4 -> columns
   // 4l..4l+3). Row indices are 32-bit (the launcher checks every operand has < 2^31 rows).
+  //
+  // The address arithmetic is kept out of the stage loop: a lane's four A source pointers
+  // (a_cur) are built once per operand of a tile (swizzled chunk, the M clamp, row * lda)
+  // and advance by kBK floats per stage; a B row is a wave-uniform pointer in scalar
+  // registers (b_cur, advancing by kBK rows) plus the lane's 16 B.
   constexpr int NW = kThreads / 64;  // waves
   constexpr int PW = 32 / NW;         // A pieces and B rows per wave per stage
   static_assert(32 % NW == 0 && kBM == 256 && kBK == 32, "staging map");
-  int32_t a_src_row[PW];   // A1 rows of the tile being loaded (through a_rows)
-  int32_t nx_src_row[PW];  // the next tile's A1 rows (index loads issued early)
-  int64_t ld_tile = tile; // the tile whose stages issue_stage reads (A2 rows dense)
+  static_assert(PW <= 8, "a piece per MFMA step");
+  int32_t nx_src_row[PW];  // A1 rows (through a_rows) of the tile whose stage 0 is issued next
+  const float* a_cur[PW];  // this lane's source of piece u in the stage issued next
+  const float* b_cur;      // B row PW * wave of the stage issued next (wave-uniform)
+  int64_t ldb_cur;
+  const uint32_t b_voff = static_cast<uint32_t>(lane) * 16u;
   const int a_slot = lane & 7;
   auto rows_of = [&](int64_t t, int32_t* a1) {
 #pragma unroll
@@ -172,32 +186,37 @@ __device__ __forceinline__ void gemm_f32_body(
       a1[u] = static_cast<int32_t>(a_rows ? a_rows[r] : r);
     }
   };
-  rows_of(tile, a_src_row);
-  auto issue_stage = [&](int s, int buf) {
-    const int k0 = s * kBK;
-    const bool first = !HAS_A2 || k0 < K1;
-    const float* Ab = first ? A1 : A2;
-    const int64_t lda = first ? lda1 : lda2;
-    const int ka = first ? k0 : k0 - K1;
-    float* sa = lds + buf * L::STAGE;
-    float* sb = sa + L::A_FL;
+  // the XOR swizzle (its own inverse) of this lane's slot in piece u, in floats
+  auto a_coff = [&](int u) { return a_chunk((PW * wave + u) * 8 + (lane >> 3), a_slot) * 4; };
+  auto point_a1 = [&](const int32_t* rows) {  // stage 0 of the tile with these A1 rows
+#pragma unroll
+    for (int u = 0; u < PW; ++u) a_cur[u] = A1 + static_cast<int64_t>(rows[u]) * lda1 + a_coff(u);
+    b_cur = B1 + static_cast<int64_t>(PW * wave) * ldb1;
+    ldb_cur = ldb1;
+  };
+  auto point_a2 = [&](int64_t t) {  // the first A2 stage of tile t (A2 rows dense)
 #pragma unroll
     for (int u = 0; u < PW; ++u) {
-      const int r = (PW * wave + u) * 8 + (lane >> 3);  // row within the tile
-      int64_t r2 = ld_tile * kBM + r;
+      int64_t r2 = t * kBM + (PW * wave + u) * 8 + (lane >> 3);
       r2 = r2 < M ? r2 : M - 1;
-      const int64_t ar = first ? static_cast<int64_t>(a_src_row[u]) : r2;
-      const int c = a_chunk(r, a_slot);  // XOR swizzle: its own inverse
-      glds16(Ab + ar * lda + ka + c * 4, sa + (PW * wave + u) * 8 * kBK);
+      a_cur[u] = A2 + r2 * lda2 + a_coff(u);
     }
-    const float* Bb = first ? B1 : B2;
-    const int64_t ldb = first ? ldb1 : ldb2;
+    b_cur = B2 + static_cast<int64_t>(PW * wave) * ldb2;
+    ldb_cur = ldb2;
+  };
+  auto advance = [&]() {  // the next stage of the same operand
 #pragma unroll
-    for (int u = 0; u < PW; ++u) {
-      const int kr = PW * wave + u;
-      if (lane < N / 4)
-        glds16(Bb + static_cast<int64_t>(ka + kr) * ldb + lane * 4, sb + b_row<L::BP>(kr));
-    }
+    for (int u = 0; u < PW; ++u) a_cur[u] += kBK;
+    b_cur += kBK * ldb_cur;
+  };
+  const uint32_t lds0 = lds_addr_of(lds);
+  auto issue_piece = [&](int u, int buf) {
+    const uint32_t sa = lds0 + static_cast<uint32_t>(buf * L::STAGE) * 4u;
+    const uint32_t sb = sa + L::A_FL * 4u;
+    glds16_to(a_cur[u], sa + static_cast<uint32_t>((PW * wave + u) * 8 * kBK) * 4u);
+    if (lane < N / 4)
+      glds16_sbase_to(b_cur + u * ldb_cur, b_voff,
+                      sb + static_cast<uint32_t>(b_row<L::BP>(PW * wave + u)) * 4u);
   };
 
   f32x4 acc[TM][TN];
@@ -206,7 +225,10 @@ __device__ __forceinline__ void gemm_f32_body(
 #pragma unroll
     for (int b = 0; b < TN; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-  issue_stage(0, 0);
+  rows_of(tile, nx_src_row);
+  point_a1(nx_src_row);
+#pragma unroll
+  for (int u = 0; u < PW; ++u) issue_piece(u, 0);
   wait_vmcnt<0>();
   __syncthreads();
   const int arow_w = wm * TM * 16;  // this wave's first row within the block tile
@@ -228,15 +250,19 @@ __device__ __forceinline__ void gemm_f32_body(
       const int buf = g & 1;
       // the next stage, in flight during this stage's MFMAs; at the tile's last stage the
       // next tile's first stage (or, for the block's last tile, a harmless re-read of this
-      // tile's first stage). Branch-free: every path issues the same loads into the same
-      // registers, so no wait is forced before the MFMAs below.
-      const bool last = s + 1 == nst;
-      const bool switch_tile = last && has_next;
-#pragma unroll
-      for (int u = 0; u < PW; ++u) a_src_row[u] = switch_tile ? nx_src_row[u] : a_src_row[u];
-      ld_tile = switch_tile ? next : ld_tile;
-      // the other buffer was last read in the previous stage (before its barrier)
-      issue_stage(last ? 0 : s + 1, buf ^ 1);
+      // tile's first stage). All three cases are block-uniform; the stage's loads are the
+      // same instructions in each.
+      if (s + 1 == nst) {
+        point_a1(nx_src_row);
+      } else if (HAS_A2 && (s + 1) * kBK == K1) {
+        point_a2(tile);
+      } else {
+        advance();
+      }
+      // the other buffer was last read in the previous stage (before its barrier), so its
+      // DMAs may go anywhere in this stage: behind the first MFMA steps, one A piece and one
+      // B row per step, so that the matrix pipe is not left idle behind the barrier while
+      // both waves of the SIMD issue their loads (the end-of-stage vmcnt(0) retires them)
       __builtin_amdgcn_sched_barrier(0);
       const float* sa = lds + buf * L::STAGE;
       const float* sb = sa + L::A_FL;
@@ -268,6 +294,11 @@ __device__ __forceinline__ void gemm_f32_body(
 #pragma unroll
             for (int b = 0; b < TN; ++b)
               acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bf[j & 1][b], acc[a][b], 0, 0, 0);
+          }
+          if (j < PW) {
+            __builtin_amdgcn_sched_barrier(0);
+            issue_piece(j, buf ^ 1);
+            __builtin_amdgcn_sched_barrier(0);
           }
         }
       }
