@@ -437,4 +437,36 @@ hipError_t dot_attn_bwd_src_f32(IType it, const int64_t* rowptr, const void* col
                                 float* dk, int64_t lddk, float* dv, int64_t lddv,
                                 hipStream_t st);
 
+// ---------------------------------------------------------------------------
+// Fused fp32 GATv2 graph attention of one relation (gatv2_f32.hip):
+// e_ij = <a, LeakyReLU(xd_i + xs_j)> per head, softmax over each destination row's edges, the
+// weighted gather of xs_j, and the exact adjoint (destination side: dxd and the partial rows
+// of da; source side over the transposed pattern: dxs). Two sources: columns >= nsplit read
+// xs2. Every feature array has its own row stride (floats); stat_m / stat_l / c share `lds`;
+// att is a contiguous 16-B aligned [C] vector. A launch needs row 0 of xd and of the first
+// gathered source to exist (padding slots read them).
+//   gatv2_da_parts: the rows P of da_part [P, C] that gatv2_bwd_dst writes (every one of
+//   them; its sum over the rows is da) — a function of (nrows, C) only.
+bool gatv2_f32_shape_ok(int C, int heads);
+int64_t gatv2_da_parts(int64_t nrows, int C);
+hipError_t gatv2_fwd_f32(IType it, const int64_t* rowptr, const void* col, int64_t nrows, int C,
+                         int heads, int64_t lds, float slope, const float* att, const float* xd,
+                         int64_t ldxd, const float* xs, int64_t ldxs, const float* xs2,
+                         int64_t ldxs2, int64_t nsplit, float* out, int64_t ldo, float beta,
+                         float* stat_m, float* stat_l, hipStream_t st);
+hipError_t gatv2_bwd_dst_f32(IType it, const int64_t* rowptr, const void* col, int64_t nrows,
+                             int C, int heads, int64_t lds, float slope, const float* att,
+                             const float* xd, int64_t ldxd, const float* xs, int64_t ldxs,
+                             const float* xs2, int64_t ldxs2, int64_t nsplit,
+                             const float* stat_m, const float* stat_l, const float* g,
+                             int64_t ldg, const float* c, float* dxd, int64_t lddxd,
+                             float* da_part, hipStream_t st);
+// rows = source rows (xs resident); col = destination ids (xd, g, stat_m, stat_l, c rows)
+hipError_t gatv2_bwd_src_f32(IType it, const int64_t* rowptr, const void* col, int64_t nrows,
+                             int C, int heads, int64_t lds, float slope, const float* att,
+                             const float* xd, int64_t ldxd, const float* g, int64_t ldg,
+                             const float* xs, int64_t ldxs, const float* stat_m,
+                             const float* stat_l, const float* c, float* dxs, int64_t lddxs,
+                             hipStream_t st);
+
 }  // namespace dgraph

@@ -4,4 +4,7 @@ def __getattr__(name):
     if name == "CommAwarePNAConv":
         from .pna import CommAwarePNAConv
         return CommAwarePNAConv
+    if name == "CommAwareGATv2Conv":
+        from .gatv2_conv import CommAwareGATv2Conv
+        return CommAwareGATv2Conv
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -4,4 +4,7 @@ def __getattr__(name):
     if name == "dot_attention":
         from .dot_attn import dot_attention
         return dot_attention
+    if name == "gatv2_attention":
+        from .gatv2 import gatv2_attention
+        return gatv2_attention
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
