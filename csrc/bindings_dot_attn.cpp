@@ -8,7 +8,8 @@
 // writes the empty-row result (zeros) with plain fills. A second source with 0 rows is
 // treated as absent, and with 0 first-source rows (nsplit = 0) every column, the padding
 // slots' column 0 included, reads the second source — so row 0 of whatever a launched
-// kernel gathers from always exists.
+// kernel gathers from always exists. The carry forward differs on the empty sides: its
+// carried state is the result, so it writes nothing there.
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
@@ -149,6 +150,39 @@ void dot_attn_fwd_op(const at::Tensor& rowptr, const at::Tensor& col, const at::
                                 cur_stream(q)));
 }
 
+// the forward from a carried (out, stat_m, stat_l). The carried state is the result of an
+// empty side: no destination rows or no source rows at all write nothing (the plain forward
+// zeroes out and stat_l there).
+void dot_attn_fwd_carry_op(const at::Tensor& rowptr, const at::Tensor& col, const at::Tensor& q,
+                           const at::Tensor& k, const at::Tensor& v,
+                           const c10::optional<at::Tensor>& k2,
+                           const c10::optional<at::Tensor>& v2, int64_t nsplit,
+                           at::Tensor& out, at::Tensor& stat_m, at::Tensor& stat_l,
+                           int64_t heads, double scale) {
+  const c10::DeviceGuard guard(q.device());
+  const int C = width(q, heads);
+  const IType it = pattern(rowptr, col, q);
+  const int64_t R = rowptr.numel() - 1;
+  const int64_t lds = stat_m.dim() == 2 ? stat_m.stride(0) : 0;
+  rows_f32(q, q, R, C, "q");
+  const Sources s = sources(q, k, v, k2, v2, nsplit, C);
+  rows_f32(out, q, R, C, "out");
+  per_head(stat_m, q, R, heads, lds, "stat_m");
+  per_head(stat_l, q, R, heads, lds, "stat_l");
+  if (R == 0) return;
+  if (s.rows == 0) {
+    TORCH_CHECK(col.numel() == 0, "dot_attn: entries but no source rows");
+    return;
+  }
+  DG_HIP_CHECK(dot_attn_fwd_carry_f32(it, rowptr.data_ptr<int64_t>(), col.data_ptr(), R, C,
+                                      static_cast<int>(heads), lds, static_cast<float>(scale),
+                                      q.data_ptr<float>(), q.stride(0), s.k, s.ldk, s.v, s.ldv,
+                                      s.k2, s.ldk2, s.v2, s.ldv2, s.nsplit,
+                                      out.data_ptr<float>(), out.stride(0),
+                                      stat_m.data_ptr<float>(), stat_l.data_ptr<float>(),
+                                      cur_stream(q)));
+}
+
 void dot_attn_bwd_dst_op(const at::Tensor& rowptr, const at::Tensor& col, const at::Tensor& q,
                          const at::Tensor& k, const at::Tensor& v,
                          const c10::optional<at::Tensor>& k2,
@@ -228,6 +262,9 @@ TORCH_LIBRARY_FRAGMENT(dgraph_amd, m) {
   m.def("dot_attn_fwd_f32(Tensor rowptr, Tensor col, Tensor q, Tensor k, Tensor v, "
         "Tensor? k2, Tensor? v2, int nsplit, Tensor(a!) out, float beta, Tensor(b!) stat_m, "
         "Tensor(c!) stat_l, int heads, float scale) -> ()");
+  m.def("dot_attn_fwd_carry_f32(Tensor rowptr, Tensor col, Tensor q, Tensor k, Tensor v, "
+        "Tensor? k2, Tensor? v2, int nsplit, Tensor(a!) out, Tensor(b!) stat_m, "
+        "Tensor(c!) stat_l, int heads, float scale) -> ()");
   m.def("dot_attn_bwd_dst_f32(Tensor rowptr, Tensor col, Tensor q, Tensor k, Tensor v, "
         "Tensor? k2, Tensor? v2, int nsplit, Tensor stat_m, Tensor stat_l, Tensor g, "
         "Tensor c, Tensor(a!) dq, int heads, float scale) -> ()");
@@ -238,6 +275,7 @@ TORCH_LIBRARY_FRAGMENT(dgraph_amd, m) {
 
 TORCH_LIBRARY_IMPL(dgraph_amd, CUDA, m) {
   m.impl("dot_attn_fwd_f32", &dgraph::dot_attn_fwd_op);
+  m.impl("dot_attn_fwd_carry_f32", &dgraph::dot_attn_fwd_carry_op);
   m.impl("dot_attn_bwd_dst_f32", &dgraph::dot_attn_bwd_dst_op);
   m.impl("dot_attn_bwd_src_f32", &dgraph::dot_attn_bwd_src_op);
 }

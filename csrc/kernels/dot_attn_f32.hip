@@ -15,7 +15,12 @@
 //   statistics pass as in gat_f32.hip: a running maximum is kept instead, and the
 //   accumulator and the running sum are rescaled once per chunk of kU edges (not per edge).
 //   Writes out, stat_m (the row maximum of e) and stat_l (1 / sum exp(e - m); 0 for an
-//   empty row, whose stat_m is unspecified).
+//   empty row, whose stat_m is unspecified). Its CARRY instantiations (dot_attn_fwd_carry)
+//   start the running maximum, sum and accumulator from an earlier pass's (out, stat_m,
+//   stat_l) instead of (0, -inf, 0): a softmax over a union of edge sets, one set per launch
+//   (interior edges while the halo is on the links, then the halo edges; several relations
+//   with their own q / k / v). The backward kernels need nothing new: they recompute alpha
+//   from the final statistics and so work on any subset of the edges.
 // * dot_attn_bwd_dst: per destination row with g_i = dL/dout_i and q_i resident: gathers
 //   k_j and v_j, ga = <g^h, v_j^h>, de = alpha (ga - c), dq_i = scale sum_j de k_j.
 //   c_i^h = sum_j alpha ga = <g_i^h, o_i^h> is an input (the caller has the forward's own
@@ -40,6 +45,10 @@
 // kernel-resource-usage; smallest .. largest of the 24 instantiations of each kernel at
 // kU = 8; no LDS, no AGPRs; 512 VGPRs per SIMD lane, so waves per SIMD = 512 / VGPRs):
 //   dot_attn_fwd      102 .. 122 VGPRs   scratch 0 B   occupancy 4     (2 kU gathered vectors)
+//   dot_attn_fwd, CARRY  104 .. 130 VGPRs   scratch 0 B   occupancy 3 .. 4
+//     (the carried state is loaded under two branches before the loop; the 24 plain
+//     instantiations compile to the same figures, SGPRs included, as without the template
+//     parameter)
 //   dot_attn_bwd_dst  109 .. 128 VGPRs   scratch 0 B   occupancy 4
 //   dot_attn_bwd_src  149 .. 178 VGPRs   scratch 0 B   occupancy 2 .. 3
 //     (4 resident / accumulator vectors, 2 kU gathered ones and 3 kU gathered statistics)
@@ -134,7 +143,12 @@ __device__ __forceinline__ const float4* vec(const float* p) {
 }
 
 // ------------------------------------------------------------------------------------ fwd
-template <typename IdxT, int LPR, int HH>
+// CARRY: the softmax state of the rows starts from an earlier pass's (out, stat_m, stat_l)
+// instead of (0, -inf, 0), so the result is the softmax over the union of the passes' edge
+// sets. stat_l == 0 on entry: nothing accumulated yet, out and stat_m are not read (they may
+// hold anything). A row without entries in this pass is left bitwise untouched and its q is
+// not loaded (its lanes still serve the wave's shuffles, with weight 0).
+template <typename IdxT, int LPR, int HH, bool CARRY>
 __global__ __launch_bounds__(256) void dot_attn_fwd_kernel(DotArgs a) {
   constexpr int G = kWave / LPR;
   constexpr int LH = LPR / HH;
@@ -152,9 +166,24 @@ __global__ __launch_bounds__(256) void dot_attn_fwd_kernel(DotArgs a) {
     const int64_t s = has_row ? a.rowptr[r] : 0;
     const int deg = has_row ? static_cast<int>(a.rowptr[r + 1] - s) : 0;
     const int maxdeg = group_imax<LPR>(deg);
-    const float4 qv = *vec(a.q + rr * a.ldq + f);
+    float4 qv;
     float m = -INFINITY, lsum = 0.f;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (CARRY) {
+      qv = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (deg > 0) {
+        qv = *vec(a.q + r * a.ldq + f);
+        const float L = a.stat_l[r * a.lds + hk];
+        if (L > 0.f) {  // out is normalised: acc = out * sum, sum = 1 / L
+          m = a.stat_m[r * a.lds + hk];
+          lsum = 1.f / L;
+          const float4 old = *vec(a.out + r * a.ldo + f);
+          acc = make_float4(old.x * lsum, old.y * lsum, old.z * lsum, old.w * lsum);
+        }
+      }
+    } else {
+      qv = *vec(a.q + rr * a.ldq + f);
+    }
     for (int k0 = 0; k0 < maxdeg; k0 += LPR) {
       const int kk = k0 + l;
       const int64_t my_c = kk < deg ? load_col<IdxT>(a, s + kk) : 0;
@@ -197,13 +226,16 @@ __global__ __launch_bounds__(256) void dot_attn_fwd_kernel(DotArgs a) {
       }
     }
     if (!has_row) continue;
+    if constexpr (CARRY) {
+      if (deg == 0) continue;  // the carried state of the row is its result
+    }
     const float inv = lsum > 0.f ? 1.f / lsum : 0.f;
     acc.x *= inv;
     acc.y *= inv;
     acc.z *= inv;
     acc.w *= inv;
     float* o = a.out + r * a.ldo + f;
-    if (a.beta != 0.f) {
+    if (!CARRY && a.beta != 0.f) {
       const float4 old = *vec(o);
       acc.x = fmaf(a.beta, old.x, acc.x);
       acc.y = fmaf(a.beta, old.y, acc.y);
@@ -344,7 +376,9 @@ template <int KIND, typename IdxT, int LPR, int HH>
 void launch_one(const DotArgs& a, int64_t blocks, hipStream_t st) {
   dim3 grid(static_cast<unsigned>(blocks)), block(256);
   if constexpr (KIND == 0)
-    hipLaunchKernelGGL((dot_attn_fwd_kernel<IdxT, LPR, HH>), grid, block, 0, st, a);
+    hipLaunchKernelGGL((dot_attn_fwd_kernel<IdxT, LPR, HH, false>), grid, block, 0, st, a);
+  else if constexpr (KIND == 3)
+    hipLaunchKernelGGL((dot_attn_fwd_kernel<IdxT, LPR, HH, true>), grid, block, 0, st, a);
   else if constexpr (KIND == 1)
     hipLaunchKernelGGL((dot_attn_bwd_dst_kernel<IdxT, LPR, HH>), grid, block, 0, st, a);
   else
@@ -413,6 +447,37 @@ hipError_t dot_attn_fwd_f32(IType it, const int64_t* rowptr, const void* col, in
   a.stat_m = stat_m;
   a.stat_l = stat_l;
   return launch<0>(a, it, heads, st);
+}
+
+hipError_t dot_attn_fwd_carry_f32(IType it, const int64_t* rowptr, const void* col,
+                                  int64_t nrows, int C, int heads, int64_t lds, float scale,
+                                  const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                  const float* v, int64_t ldv, const float* k2, int64_t ldk2,
+                                  const float* v2, int64_t ldv2, int64_t nsplit, float* out,
+                                  int64_t ldo, float* stat_m, float* stat_l, hipStream_t st) {
+  DotArgs a{};
+  a.rowptr = rowptr;
+  a.col = col;
+  a.nrows = nrows;
+  a.C = C;
+  a.lds = lds;
+  a.scale = scale;
+  a.q = q;
+  a.ldq = ldq;
+  a.k = k;
+  a.ldk = ldk;
+  a.v = v;
+  a.ldv = ldv;
+  a.k2 = k2;
+  a.ldk2 = ldk2;
+  a.v2 = v2;
+  a.ldv2 = ldv2;
+  a.nsplit = nsplit;
+  a.out = out;
+  a.ldo = ldo;
+  a.stat_m = stat_m;
+  a.stat_l = stat_l;
+  return launch<3>(a, it, heads, st);
 }
 
 hipError_t dot_attn_bwd_dst_f32(IType it, const int64_t* rowptr, const void* col,

@@ -420,6 +420,17 @@ hipError_t dot_attn_fwd_f32(IType it, const int64_t* rowptr, const void* col, in
                             int64_t ldv, const float* k2, int64_t ldk2, const float* v2,
                             int64_t ldv2, int64_t nsplit, float* out, int64_t ldo, float beta,
                             float* stat_m, float* stat_l, hipStream_t st);
+// The forward started from the rows' carried softmax state instead of (0, -inf, 0): on entry
+// stat_l = 1 / sum of the earlier passes (0: nothing yet; out and stat_m are then not read),
+// out their normalised result and stat_m their maximum; on return the three hold the
+// softmax over the union of the earlier passes' entries and this pattern's. Rows without
+// entries in this pattern are left bitwise untouched (their q is not read).
+hipError_t dot_attn_fwd_carry_f32(IType it, const int64_t* rowptr, const void* col,
+                                  int64_t nrows, int C, int heads, int64_t lds, float scale,
+                                  const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                  const float* v, int64_t ldv, const float* k2, int64_t ldk2,
+                                  const float* v2, int64_t ldv2, int64_t nsplit, float* out,
+                                  int64_t ldo, float* stat_m, float* stat_l, hipStream_t st);
 hipError_t dot_attn_bwd_dst_f32(IType it, const int64_t* rowptr, const void* col,
                                 int64_t nrows, int C, int heads, int64_t lds, float scale,
                                 const float* q, int64_t ldq, const float* k, int64_t ldk,

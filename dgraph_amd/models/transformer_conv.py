@@ -16,9 +16,18 @@ MI355X formulation (with a :class:`~dgraph_amd.data.hetero.RelationGraph`):
   backward), issued on every rank whether or not it receives rows; the received rows are
   read as a second source, never concatenated with the local ones;
 * the attention itself is :func:`~dgraph_amd.ops.dot_attn.dot_attention`: three fused
-  kernels, no per-edge tensor (GPU fp32), or its fp64 plain-PyTorch evaluation (CPU).
+  kernels, no per-edge tensor (GPU fp32), or its fp64 plain-PyTorch evaluation (CPU);
+* ``overlap=True`` (more than one rank) moves the exchange inside the attention op
+  (:func:`~dgraph_amd.ops.dot_attn.dot_attention_halo`): the interior edges are attended
+  over while the ``[k | v]`` rows are on the links and the halo edges are folded into the
+  same softmax when they land (the kernel's carry-in forward); in backward the halo rows'
+  gradient is computed first and returns to its owners under ``dq`` and the local ``dk`` /
+  ``dv``. Still one exchange forward and one backward on every rank. The default is the
+  synchronous exchange: the overlapped path has only been timed against a link model on
+  one GPU (PERFORMANCE.md), not on a multi-GPU node.
 
-Out of scope here: wiring the layer into ``CommAwareRGAT``, the lean ``HeteroGraph`` path or
+Out of scope here: the same overlap for the GAT and GATv2 layers (their kernels have no carry-in
+forward yet); wiring the layer into ``CommAwareRGAT``, the lean ``HeteroGraph`` path or
 the OGB-LSC trainer; bf16; edge features; PyG's ``beta`` gate between the skip and the
 attention output; attention dropout.
 """
@@ -27,20 +36,22 @@ from __future__ import annotations
 import torch
 import torch.nn as nn
 
-from ..ops.dot_attn import dot_attention
+from ..ops.dot_attn import HaloPlan, dot_attention, dot_attention_halo
 from ..ops.gat import GatPattern
 from .rgat import _world
 
 
 class CommAwareTransformerConv(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, comm=None, heads: int = 1,
-                 bias: bool = True, root_weight: bool = True, hetero: bool = False):
+                 bias: bool = True, root_weight: bool = True, hetero: bool = False,
+                 overlap: bool = False):
         super().__init__()
         if out_channels % heads:
             raise ValueError("out_channels must be divisible by heads")
         self.comm = comm
         self.heads = heads
         self.hetero = hetero
+        self.overlap = overlap
         self.out_channels = out_channels
         self.lin_query = nn.Linear(in_channels, out_channels)
         self.lin_kv = nn.Linear(in_channels, 2 * out_channels)  # rows [W_k ; W_v]
@@ -68,16 +79,23 @@ class CommAwareTransformerConv(nn.Module):
         C = self.out_channels
         q = self.lin_query(x)
         kv = self.lin_kv(x_j if (self.hetero and x_j is not None) else x)
-        kh = vh = None
-        if _world(self.comm) > 1:  # collective on every rank of the relation's group
-            from ..parallel.halo import HaloExchange
+        pat = self._pattern(graph)
+        if _world(self.comm) > 1 and self.overlap:  # the exchange runs inside the op
+            plan = graph._cache.get("dot_attn_halo_plan")
+            if plan is None or plan.send_map.num_src != kv.shape[0]:
+                plan = HaloPlan.from_pattern(self.comm, graph.pattern, kv.shape[0])
+                graph._cache["dot_attn_halo_plan"] = plan
+            out = dot_attention_halo(q, kv, pat, plan, heads=self.heads)
+        else:
+            kh = vh = None
+            if _world(self.comm) > 1:  # collective on every rank of the relation's group
+                from ..parallel.halo import HaloExchange
 
-            if self._halo is None:
-                self._halo = HaloExchange(self.comm)
-            halo = self._halo(kv, graph.pattern)
-            kh, vh = halo[:, :C], halo[:, C:]
-        out = dot_attention(q, kv[:, :C], kv[:, C:], self._pattern(graph), kh, vh,
-                            heads=self.heads)
+                if self._halo is None:
+                    self._halo = HaloExchange(self.comm)
+                halo = self._halo(kv, graph.pattern)
+                kh, vh = halo[:, :C], halo[:, C:]
+            out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads)
         if self.lin_skip is not None:
             out = out + self.lin_skip(x)
         if self.bias is not None:

@@ -4,6 +4,9 @@ def __getattr__(name):
     if name == "dot_attention":
         from .dot_attn import dot_attention
         return dot_attention
+    if name in ("dot_attention_parts", "dot_attention_halo", "HaloPlan"):
+        from . import dot_attn
+        return getattr(dot_attn, name)
     if name == "gatv2_attention":
         from .gatv2 import gatv2_attention
         return gatv2_attention

@@ -72,6 +72,27 @@ class GatPattern:
         t = _transpose_noperm(CSR(self.rowptr, self.col, ncols))
         self.t_rowptr = t.rowptr.long().contiguous()
         self.t_col = t.col.to(torch.int32).contiguous()
+        self._split = None
+
+    def split(self):
+        """``(interior, halo)``: two one-source patterns over the same ``R`` rows, each with
+        its own transpose, built once. ``interior`` keeps every row's entries with a column
+        below ``nsplit`` (over ``nsplit`` columns), ``halo`` the others with their columns
+        rebased to ``[0, H)`` (over ``H`` columns; no entries when there are no halo rows).
+        Per row, the two together hold the merged pattern's entries, each part in the merged
+        pattern's order."""
+        if self._split is None:
+            deg = self.rowptr[1:] - self.rowptr[:-1]
+            rows = torch.repeat_interleave(torch.arange(self.R, device=deg.device), deg)
+            col = self.col.long()
+            far = col >= self.nsplit
+            parts = []
+            for sel, shift, ncols in ((~far, 0, self.nsplit), (far, self.nsplit, self.H)):
+                rp = torch.zeros(self.R + 1, dtype=torch.long, device=deg.device)
+                rp[1:] = torch.cumsum(torch.bincount(rows[sel], minlength=self.R), 0)
+                parts.append(GatPattern(rp, col[sel] - shift, ncols, 0))
+            self._split = tuple(parts)
+        return self._split
 
     @staticmethod
     def merged(interior: CSR, halo: Optional[CSR], nsplit: int) -> "GatPattern":
