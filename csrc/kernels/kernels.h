@@ -182,6 +182,35 @@ hipError_t segment_pna_bwd(IType it, const int64_t* t_rowptr, const void* t_col,
                            int64_t nrows, int F, bool halo, float beta, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
+// Fused softmax neighbourhood aggregation (spmm_softmax.hip), fp32: PyG's
+// SoftmaxAggregation with a per-channel temperature t [F] (contiguous). For CSR row r
+// (output row row_map[r] when given), with s_k = t[f] * x[col[k], f] over the row's entries:
+//   lse[r, f] = log sum_k exp(s_k)                       (-inf for an empty row)
+//   out[r, f] = sum_k exp(s_k - lse[r, f]) x[col[k], f]  (0 for an empty row)
+// evaluated with a running maximum (no overflow for any t x). Every array has its own row
+// stride, unit column stride. Two sources: the second pass (second = true) starts from the
+// incumbent (out, lse) of the first; a row without an entry in the second pass is not
+// written, an incumbent of lse = -inf counts as empty.
+// Backward over the transposed pattern of any subset of the entries, given the FINAL
+// (out, lse) (row c = source row of x, t_col = destination rows of g / out_fwd / lse):
+//   w = exp(t[f] x[c, f] - lse[r, f]),  d = x[c, f] - out_fwd[r, f],  r = t_col[k]
+//   dx[c, f] = sum_k w g[r, f] (1 + t[f] d)
+//   dt[f]    = sum_c sum_k w g[r, f] d^2  = the column sums of dt_part
+// dt_part is [segment_softmax_dt_parts(nrows), F] contiguous, one fixed-order partial row
+// per workgroup, every row written; null skips it. No atomics; bitwise reproducible.
+// ---------------------------------------------------------------------------
+int64_t segment_softmax_dt_parts(int64_t nrows);
+hipError_t segment_softmax_fwd(IType it, const int64_t* rowptr, const void* col, const float* x,
+                               int64_t ldx, const float* t, float* out, int64_t ldo, float* lse,
+                               int64_t ldl, int64_t nrows, int F, bool second,
+                               const int64_t* row_map, hipStream_t stream);
+hipError_t segment_softmax_bwd(IType it, const int64_t* t_rowptr, const void* t_col,
+                               const float* x, int64_t ldx, const float* t, const float* g,
+                               int64_t ldg, const float* out_fwd, int64_t ldof,
+                               const float* lse, int64_t ldl, float* dx, int64_t lddx,
+                               float* dt_part, int64_t nrows, int F, hipStream_t stream);
+
+// ---------------------------------------------------------------------------
 // Row copy with optional source and destination index (K4/K7/K8 replacement, K-new-1).
 //   out[dst(i)] (+)= x[src(i)]   for i in [0, n)
 // src/dst null == identity. src(i) < 0 writes zeros; dst(i) < 0 skips the row.

@@ -7,4 +7,7 @@ def __getattr__(name):
     if name == "CommAwareGATv2Conv":
         from .gatv2_conv import CommAwareGATv2Conv
         return CommAwareGATv2Conv
+    if name == "CommAwareGENConv":
+        from .genconv import CommAwareGENConv
+        return CommAwareGENConv
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

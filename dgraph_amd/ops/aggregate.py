@@ -4,6 +4,8 @@
   same kernel on the cached transposed CSR (or on the same CSR for symmetric patterns).
 * :func:`aggregate_multi` — mean, max, min and standard deviation of the same neighbour
   rows in ONE gather pass (the PNA aggregators), as column blocks of one ``[R, A*F]`` tensor.
+* :func:`softmax_aggregate` — the learnable softmax aggregation (per channel, the score is
+  the value times a temperature) in one gather pass, with the temperature's gradient.
 * :func:`gather` / :func:`scatter_sum` — vertex->edge gather and edge->vertex scatter-sum
   over a static :class:`~dgraph_amd.ops.csr.IndexMap`; each is the other's adjoint
   (the core contract of the reference, tests/test_NCCLCommPlan.py:100-111,297-307),
@@ -167,6 +169,58 @@ def aggregate_multi(x: torch.Tensor, csr: CSR, aggregators=PNA_AGGREGATORS,
     return _AggregateMultiFn.apply(vec_rows(x), csr, aggs, float(eps))
 
 
+def as_temperature(t, x: torch.Tensor) -> torch.Tensor:
+    """The temperature of a softmax aggregation as a tensor: a float becomes a ``[1]`` tensor
+    of ``x``'s dtype on its device; a tensor must be 0-d, ``[1]`` or ``[F]``."""
+    if not isinstance(t, torch.Tensor):
+        return torch.full((1,), float(t), dtype=x.dtype, device=x.device)
+    if t.numel() != 1 and (t.dim() != 1 or t.numel() != x.shape[1]):
+        raise ValueError(f"t must be a scalar, [1] or [{x.shape[1]}], got {tuple(t.shape)}")
+    return t
+
+
+def temperature_grad(partials: torch.Tensor, t: torch.Tensor) -> torch.Tensor:
+    """``dt`` in ``t``'s shape and dtype from the ``[P, F]`` partial rows of the backward
+    kernel (a scalar temperature receives the sum over the channels)."""
+    dt = partials.sum(0)
+    if t.numel() == 1:
+        dt = dt.sum()
+    return dt.reshape(t.shape).to(t.dtype)
+
+
+class _SoftmaxAggregateFn(Function):
+    """Softmax aggregation (K.segment_softmax). ``(out, lse)`` is all the forward keeps; the
+    backward recomputes every weight in one gather over the transposed pattern, which gives
+    ``dx`` and the partial rows of ``dt`` together."""
+
+    @staticmethod
+    def forward(ctx, x, t, csr: CSR):
+        out, lse = K.segment_softmax(csr.rowptr, csr.col, x, t)
+        ctx.csr = csr
+        ctx.save_for_backward(x, t, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, out, lse = ctx.saved_tensors
+        tr = ctx.csr.transpose()
+        want_dt = ctx.needs_input_grad[1]
+        dx, part = K.segment_softmax_bwd(tr.rowptr, tr.col, x, t, vec_rows(g), out, lse,
+                                         want_dt=want_dt)
+        return dx, (temperature_grad(part, t) if want_dt else None), None
+
+
+def softmax_aggregate(x: torch.Tensor, csr: CSR, t=1.0) -> torch.Tensor:
+    """Softmax aggregation (PyG's ``SoftmaxAggregation``, the aggregator of ``GENConv``):
+    ``out[r, f] = sum_j softmax_j(t_f x[j, f]) x[j, f]`` over the entries ``j`` of row ``r``
+    (0 for an empty row). The softmax is per channel and its score is the value itself:
+    ``t = 0`` is the mean, ``t -> +inf`` / ``-inf`` the max / min. ``t``: a float, a 0-d or
+    ``[1]`` tensor, or an ``[F]`` tensor; it may require grad (a scalar receives the sum of
+    the per-channel gradient). On the GPU (fp32) one kernel gathers each neighbour row once
+    and writes nothing per edge, and one kernel computes ``dx`` and ``dt``."""
+    return _SoftmaxAggregateFn.apply(vec_rows(x), as_temperature(t, x), csr)
+
+
 def aggregate(
     x: torch.Tensor,
     csr: CSR,
@@ -186,7 +240,16 @@ def aggregate(
     ``reduce="std"``: the population standard deviation over a row's entries,
     ``sqrt(mean((x_j - mean)^2) + 1e-5)``, unweighted and single-head: the ``"std"`` block of
     :func:`aggregate_multi`, which computes several of these from one pass.
+
+    ``reduce="softmax"``: :func:`softmax_aggregate` at temperature 1, unweighted and
+    single-head.
     """
+    if reduce == "softmax":
+        if edge_weight is not None:
+            raise ValueError("reduce='softmax' takes no edge weights")
+        if heads != 1:
+            raise ValueError(f"reduce='softmax' takes one head, got heads={heads}")
+        return softmax_aggregate(x, csr, 1.0)
     if reduce == "std":
         if edge_weight is not None:
             raise ValueError("reduce='std' takes no edge weights")

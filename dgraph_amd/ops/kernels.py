@@ -234,6 +234,98 @@ def segment_pna_bwd(
                                 sdev, g_max, amax, g_min, amin, halo, beta)
 
 
+def temperature_rows(t, x: torch.Tensor, name: str) -> torch.Tensor:
+    """The temperature as a contiguous ``[F]`` vector of ``x``'s dtype on its device (a
+    float or a one-element tensor is expanded)."""
+    F = x.shape[1]
+    if not isinstance(t, torch.Tensor):
+        return torch.full((F,), float(t), dtype=x.dtype, device=x.device)
+    t = t.detach().to(device=x.device, dtype=x.dtype)
+    if t.numel() == 1:
+        return t.reshape(1).expand(F).contiguous()
+    if t.dim() != 1 or t.numel() != F:
+        raise ValueError(f"{name}: t must be a scalar or [{F}], got {tuple(t.shape)}")
+    return t.contiguous()
+
+
+def segment_softmax(
+    rowptr: torch.Tensor,
+    col: torch.Tensor,
+    x: torch.Tensor,
+    t,
+    out: Optional[torch.Tensor] = None,
+    lse: Optional[torch.Tensor] = None,
+    *,
+    second: bool = False,
+    row_map: Optional[torch.Tensor] = None,
+):
+    """Softmax aggregation of each CSR row's entries in ONE pass over the neighbour rows:
+    with ``s_k = t[f] * x[col[k], f]``, ``out[r, f] = sum_k softmax_k(s)_k x[col[k], f]`` and
+    ``lse[r, f] = log sum_k exp(s_k)`` (0 and ``-inf`` for an empty row), about a running
+    maximum (no overflow for any ``t x``). ``t``: ``[F]`` (a scalar is expanded), any sign.
+    ``(out, lse)`` is the whole state: every weight is ``exp(t x[c] - lse[r])``.
+
+    ``second``: ``out`` / ``lse`` hold the result of an earlier pass over another source (the
+    interior block), which this pass starts from; a row without an entry here is left
+    bitwise as it is. ``row_map`` as in :func:`spmm`. Returns ``(out, lse)``."""
+    R = rowptr.numel() - 1
+    F = x.shape[1]
+    if (second or row_map is not None) and (out is None or lse is None):
+        raise ValueError("segment_softmax: second / row_map need explicit out and lse")
+    t = temperature_rows(t, x, "segment_softmax")
+    if out is None:
+        out = torch.empty(R, F, dtype=x.dtype, device=x.device)
+    if lse is None:
+        lse = torch.empty(out.shape[0], F, dtype=x.dtype, device=x.device)
+    if _native_ok(x):
+        _native.ops().segment_softmax_fwd(rowptr, col, x, t, out, lse, bool(second), row_map)
+        return out, lse
+    return _ref.segment_softmax(rowptr, col, x, t, out, lse, second, row_map)
+
+
+def segment_softmax_bwd(
+    t_rowptr: torch.Tensor,
+    t_col: torch.Tensor,
+    x: torch.Tensor,
+    t,
+    g: torch.Tensor,
+    out_fwd: torch.Tensor,
+    lse: torch.Tensor,
+    out: Optional[torch.Tensor] = None,
+    want_dt: bool = True,
+    *,
+    dt_partials: Optional[torch.Tensor] = None,
+):
+    """Backward of :func:`segment_softmax` as a gather over the transposed pattern
+    (``t_rowptr`` / ``t_col``: rows = source rows of ``x``, columns = destination rows of
+    ``g`` / ``out_fwd`` / ``lse``) of ANY subset of the entries, given the final
+    ``(out_fwd, lse)``: per entry ``w = exp(t x[c] - lse[r])``, ``d = x[c] - out_fwd[r]``,
+    ``dx[c] = sum_k w g[r] (1 + t d)`` and ``dt = sum_c sum_k w g[r] d^2``. ``dt`` comes as
+    fixed-order partial rows ``[P, F]`` (one per workgroup; ``dt = partials.sum(0)``) in
+    ``dt_partials`` when given (the GPU needs ``P = segment_softmax_dt_parts(rows)``), else
+    a fresh buffer; ``want_dt=False`` skips it and touches no buffer. No atomics.
+    Returns ``(dx, partials or None)``."""
+    C = t_rowptr.numel() - 1
+    F = x.shape[1]
+    t = temperature_rows(t, x, "segment_softmax_bwd")
+    if out is None:
+        out = torch.empty(C, F, dtype=x.dtype, device=x.device)
+    if _native_ok(x):
+        ops = _native.ops()
+        part = None
+        if want_dt:
+            part = dt_partials if dt_partials is not None else torch.empty(
+                ops.segment_softmax_dt_parts(C), F, dtype=torch.float32, device=x.device)
+        ops.segment_softmax_bwd(t_rowptr, t_col, x, t, g, out_fwd, lse, out, part)
+        return out, part
+    dx, part = _ref.segment_softmax_bwd(t_rowptr, t_col, x, t, g, out_fwd, lse, out, want_dt)
+    if part is not None and dt_partials is not None:
+        dt_partials.zero_()
+        dt_partials[:1] = part.to(dt_partials.dtype)
+        part = dt_partials
+    return dx, part
+
+
 def copy_rows(
     x: torch.Tensor,
     src_idx: Optional[torch.Tensor] = None,

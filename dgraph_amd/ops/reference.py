@@ -241,6 +241,78 @@ def segment_pna_bwd(t_rowptr, t_col, rel, x, inv_deg, out, g_mean=None, g_std=No
     return out
 
 
+def segment_softmax(rowptr, col, x, t, out, lse, second=False, row_map=None):
+    """Softmax aggregation of each CSR row's entries (cf. kernels.h): with ``s = t[f] *
+    x[col[k], f]``, ``lse = log sum_k exp(s)`` (-inf for an empty row) and ``out = sum_k
+    exp(s - lse) x[col[k]]`` (0 for an empty row), evaluated about the row maximum.
+    ``second``: ``(out, lse)`` hold an incumbent, which enters as one more entry of value
+    ``out`` and weight ``exp(lse)``; a row without an entry here keeps it bitwise. fp32
+    (fp64 for fp64 input)."""
+    R = rowptr.numel() - 1
+    F = x.shape[1]
+    if R <= 0 or F == 0:
+        return out, lse
+    cdt = torch.float64 if x.dtype == torch.float64 else torch.float32
+    dev = x.device
+    rows = _row_ids(rowptr)
+    vals = x.to(cdt)[col.long()]
+    s = vals * t.to(cdt)
+    ninf = float("-inf")
+    tgt = slice(0, R) if row_map is None else row_map.long()
+    m = torch.full((R, F), ninf, dtype=cdt, device=dev)
+    if second:
+        m0, o0 = lse[tgt].to(cdt), out[tgt].to(cdt)
+        m = m0.clone()
+    m.scatter_reduce_(0, rows.unsqueeze(1).expand(-1, F), s, "amax", include_self=True)
+    ms = torch.where(m == ninf, torch.zeros((), dtype=cdt, device=dev), m)  # empty rows
+    w = torch.exp(s - ms[rows])
+    l = torch.zeros(R, F, dtype=cdt, device=dev)
+    acc = torch.zeros(R, F, dtype=cdt, device=dev)
+    if second:  # the incumbent comes first
+        k = torch.where(m0 == ninf, torch.zeros((), dtype=cdt, device=dev), torch.exp(m0 - ms))
+        l += k
+        acc += k * o0
+    l.index_add_(0, rows, w)
+    acc.index_add_(0, rows, w * vals)
+    has = l > 0
+    one = torch.ones((), dtype=cdt, device=dev)
+    new_out = torch.where(has, acc / torch.where(has, l, one), torch.zeros((), dtype=cdt,
+                                                                           device=dev))
+    new_lse = torch.where(has, ms + torch.log(torch.where(has, l, one)),
+                          torch.full((), ninf, dtype=cdt, device=dev))
+    if second:
+        visited = ((rowptr[1:] - rowptr[:-1]) > 0).unsqueeze(1)
+        new_out = torch.where(visited, new_out, o0)
+        new_lse = torch.where(visited, new_lse, m0)
+    out[tgt] = new_out.to(out.dtype)
+    lse[tgt] = new_lse.to(lse.dtype)
+    return out, lse
+
+
+def segment_softmax_bwd(t_rowptr, t_col, x, t, g, out_fwd, lse, dx, want_dt=True):
+    """Backward of :func:`segment_softmax` over the transposed pattern of any subset of the
+    entries, given the final ``(out_fwd, lse)`` (cf. kernels.h): per entry ``w = exp(t x[c] -
+    lse[r])``, ``d = x[c] - out_fwd[r]``; ``dx[c] = sum w g[r] (1 + t d)`` and the one
+    partial row ``sum w g[r] d^2`` of ``dt``. Returns ``(dx, [1, F] partials or None)``."""
+    C = t_rowptr.numel() - 1
+    F = dx.shape[1]
+    cdt = torch.float64 if dx.dtype == torch.float64 else torch.float32
+    part = torch.zeros(1, F, dtype=cdt, device=dx.device) if want_dt else None
+    if C <= 0 or F == 0:
+        return dx, part
+    src = _row_ids(t_rowptr)
+    r = t_col.long()
+    tt = t.to(cdt)
+    xs = x.to(cdt)[src]
+    wg = torch.exp(tt * xs - lse.to(cdt)[r]) * g.to(cdt)[r]
+    d = xs - out_fwd.to(cdt)[r]
+    acc = torch.zeros(C, F, dtype=cdt, device=dx.device).index_add_(0, src, wg * (1 + tt * d))
+    dx[:C] = acc.to(dx.dtype)
+    if want_dt:
+        part = (wg * d * d).sum(0, keepdim=True)
+    return dx, part
+
+
 def copy_rows(
     x: torch.Tensor,
     src_idx: Optional[torch.Tensor],

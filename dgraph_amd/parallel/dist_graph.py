@@ -25,7 +25,7 @@ from torch.autograd import Function
 
 from ..comm.alltoallv import AllToAllV
 from ..ops import kernels as K
-from ..ops.aggregate import check_aggregators, multi_blocks, vec_rows
+from ..ops.aggregate import as_temperature, check_aggregators, multi_blocks, vec_rows
 from ..ops.csr import CSR, IndexMap
 
 
@@ -568,6 +568,108 @@ class DistGraph:
             K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
         return out
 
+    def aggregate_softmax(self, x: torch.Tensor, t: torch.Tensor,
+                          halo_rows: Optional[torch.Tensor] = None):
+        """Softmax aggregation over in-neighbours, local and halo (``out[r, f] = sum_j
+        softmax_j(t_f x[j, f]) x[j, f]``, :func:`~dgraph_amd.ops.kernels.segment_softmax`),
+        on the schedule of :meth:`aggregate_multi`: the interior pass runs while the halo
+        rows are on the links, then the halo block is run over all ``L`` rows starting from
+        the interior's ``(out, lse)``. ``t``: the ``[F]`` temperature. Returns ``(out,
+        saved)``; ``saved`` is what :meth:`aggregate_softmax_T` needs (``out``, ``lse`` and
+        ``halo``, the halo rows this pass read). ``halo_rows`` as in :meth:`aggregate`."""
+        self.edges_aggregated += self.nnz
+        L, F = self.L, x.shape[1]
+        it = self.interior
+        out = torch.empty(L, F, dtype=x.dtype, device=x.device)
+        lse = torch.empty(L, F, dtype=x.dtype, device=x.device)
+        saved = dict(out=out, lse=lse, halo=None)
+        if self.halo is None or halo_rows is not None:
+            K.segment_softmax(it.rowptr, it.col, x, t, out, lse)
+            if self.halo is not None:
+                K.segment_softmax(self.halo.rowptr, self.halo.col, halo_rows, t, out, lse,
+                                  second=True)
+            saved["halo"] = halo_rows
+            return out, saved
+        # the exchanges depend on the plan alone (a rank with sends and no halo entry posts
+        # them too); column chunks as in aggregate()
+        pend = []
+        for c0, c1 in self._col_chunks(self.a2a, F, x.element_size()):
+            xc = x if (c0, c1) == (0, F) else x[:, c0:c1]
+            recv, work = self.a2a(K.gather_rows(xc, self.send_map.idx), async_op=True)
+            if not self.overlap:
+                work.wait()
+            pend.append((c0, c1, recv, work))
+        K.segment_softmax(it.rowptr, it.col, x, t, out, lse)
+        for c0, c1, recv, work in pend:
+            work.wait()
+            whole = (c0, c1) == (0, F)
+            K.segment_softmax(self.halo.rowptr, self.halo.col, recv, t if whole else t[c0:c1],
+                              out if whole else out[:, c0:c1],
+                              lse if whole else lse[:, c0:c1], second=True)
+        saved["halo"] = pend[0][2] if len(pend) == 1 else torch.cat([p[2] for p in pend], 1)
+        return out, saved
+
+    def aggregate_softmax_T(self, g: torch.Tensor, x: torch.Tensor, t: torch.Tensor,
+                            saved: dict, out: Optional[torch.Tensor] = None,
+                            halo_out: Optional[torch.Tensor] = None, want_dt: bool = True):
+        """Backward of :meth:`aggregate_softmax` (``g``: ``[L, F]``; ``x``, ``t`` and
+        ``saved``: the forward's inputs and second result). Every weight is recomputed from
+        the final ``(out, lse)``: the interior entries over the interior's transposed
+        pattern with ``x``, the halo block's over its transposed pattern with the kept halo
+        rows into ``[H, F]`` rows, which then take the reverse path of
+        :meth:`aggregate_multi_T` (reverse exchange under the interior pass, owner-side
+        segment sum). ``halo_out``: ``[H, F]`` buffer that keeps the halo gradient here.
+        Returns ``(dx, dt)``; ``dt`` (``[F]``, or ``None`` without ``want_dt``) is this
+        rank's part: the sum over its interior and halo entries, to be all-reduced with the
+        other replicated parameters' gradients."""
+        g = vec_rows(g)
+        F = x.shape[1]
+        it = self.interior if self.interior.symmetric else self.interior.transpose()
+        self.edges_aggregated += it.nnz + (self.halo.nnz if self.halo is not None else 0)
+        of, lse = saved["out"], saved["lse"]
+        dt = None
+
+        def add_dt(part, c0=0, c1=F):
+            nonlocal dt
+            if part is None:
+                return
+            if dt is None:
+                dt = torch.zeros(F, dtype=part.dtype, device=part.device)
+            dt[c0:c1] += part.sum(0)
+
+        if self.halo is None:
+            dx, part = K.segment_softmax_bwd(it.rowptr, it.col, x, t, g, of, lse, out, want_dt)
+            add_dt(part)
+            return dx, dt
+        ht = self.halo.transpose()
+        xh = saved["halo"]
+        if halo_out is not None:
+            _, part = K.segment_softmax_bwd(ht.rowptr, ht.col, xh, t, g, of, lse, halo_out,
+                                            want_dt)
+            add_dt(part)
+            dx, part = K.segment_softmax_bwd(it.rowptr, it.col, x, t, g, of, lse, out, want_dt)
+            add_dt(part)
+            return dx, dt
+        pend = []
+        for c0, c1 in self._col_chunks(self.a2a_rev, F, g.element_size()):
+            whole = (c0, c1) == (0, F)
+            cut = (lambda v: v) if whole else (lambda v: v[:, c0:c1])  # noqa: E731
+            hg, part = K.segment_softmax_bwd(ht.rowptr, ht.col, cut(xh), t if whole else t[c0:c1],
+                                             cut(g), cut(of), cut(lse), None, want_dt)
+            add_dt(part, c0, c1)
+            sg, work = self.a2a_rev(hg, async_op=True)
+            if not self.overlap:
+                work.wait()
+            pend.append((c0, c1, sg, work))
+        dx, part = K.segment_softmax_bwd(it.rowptr, it.col, x, t, g, of, lse, out, want_dt)
+        add_dt(part)
+        st = self.send_map.transpose_csr().compact_rows()
+        for c0, c1, sg, work in pend:
+            work.wait()
+            oc = dx if (c0, c1) == (0, F) else dx[:, c0:c1]
+            K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
+        return dx, dt
+
     def _peers(self) -> bool:
         """True when the plan's peers exist (a process group of the plan's size)."""
         import torch.distributed as dist
@@ -825,13 +927,46 @@ def dist_aggregate_multi(x: torch.Tensor, graph: DistGraph,
     return _DistAggregateMultiFn.apply(x, graph, check_aggregators(aggregators), float(eps))
 
 
+class _DistSoftmaxAggregateFn(Function):
+    @staticmethod
+    def forward(ctx, x, t, graph: DistGraph):
+        x = vec_rows(x)
+        tv = K.temperature_rows(t, x, "dist_softmax_aggregate")
+        out, saved = graph.aggregate_softmax(x, tv)
+        ctx.graph = graph
+        ctx.save_for_backward(x, t, out, saved["lse"], saved["halo"])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, t, out, lse, halo = ctx.saved_tensors
+        tv = K.temperature_rows(t, x, "dist_softmax_aggregate")
+        want_dt = ctx.needs_input_grad[1]
+        dx, dt = ctx.graph.aggregate_softmax_T(g, x, tv, dict(out=out, lse=lse, halo=halo),
+                                               want_dt=want_dt)
+        if want_dt:
+            dt = (dt.sum() if t.numel() == 1 else dt).reshape(t.shape).to(t.dtype)
+        return dx, dt, None
+
+
+def dist_softmax_aggregate(x: torch.Tensor, graph: DistGraph, t=1.0) -> torch.Tensor:
+    """Autograd-aware distributed :func:`~dgraph_amd.ops.aggregate.softmax_aggregate` over
+    every local vertex's in-neighbours, local and halo (one exchange forward, one backward;
+    :meth:`DistGraph.aggregate_softmax`). ``t`` as there; its gradient is this rank's part
+    (``t`` is a replicated parameter: all-reduce it with the other weight gradients)."""
+    return _DistSoftmaxAggregateFn.apply(x, as_temperature(t, x), graph)
+
+
 def dist_aggregate(x: torch.Tensor, graph: DistGraph, mean: bool = True,
                    reduce: Optional[str] = None) -> torch.Tensor:
     """Autograd-aware distributed neighbourhood aggregation: sum or mean (``mean``), or
     with ``reduce="max"`` / ``"min"`` the elementwise extremum over the in-neighbours (its
-    gradient goes to the one winning entry, :meth:`DistGraph.aggregate_extreme`)."""
+    gradient goes to the one winning entry, :meth:`DistGraph.aggregate_extreme`), or with
+    ``reduce="softmax"`` :func:`dist_softmax_aggregate` at temperature 1."""
     if reduce is None:
         return _DistAggregateFn.apply(x, graph, mean)
+    if reduce == "softmax":
+        return dist_softmax_aggregate(x, graph, 1.0)
     if reduce not in ("max", "min"):
         raise ValueError(f"unsupported reduce {reduce!r}")
     return _DistAggregateExtremeFn.apply(x, graph, reduce == "min")
