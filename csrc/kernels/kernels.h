@@ -478,6 +478,41 @@ hipError_t dot_attn_bwd_src_f32(IType it, const int64_t* rowptr, const void* col
                                 hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// The same attention with a per-edge term in key and value (dot_attn_edge_f32.hip; PyG's
+// TransformerConv with edge_dim): kk = k_j + ee_p, vv = v_j + ee_p with p the entry's CSR
+// slot, then as above with kk / vv for k_j / v_j. ee [E, C] is read in slot order (a row's
+// slots are consecutive rows of ee). The destination side also writes the per-edge gradient
+// dee [E, C] and, per slot and head, w [E, 2 heads] = (alpha | de without scale): every real
+// slot has exactly one writer, so dee and w need no initialisation. The source side reads
+// only q, g and w: dv_j = sum alpha g_i, dk_j = scale sum de q_i over the transposed
+// pattern, whose entry p' finds its weights at row t_slot[p'] of w (t_slot has col's index
+// type and is indexed by absolute position, as col is). A launch needs row 0 of q, of the
+// first gathered source, of ee and of w to exist (padding slots read them with weight 0).
+hipError_t dot_attn_edge_fwd_f32(IType it, const int64_t* rowptr, const void* col,
+                                 int64_t nrows, int C, int heads, int64_t lds, float scale,
+                                 const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                 const float* v, int64_t ldv, const float* k2, int64_t ldk2,
+                                 const float* v2, int64_t ldv2, int64_t nsplit,
+                                 const float* ee, int64_t ldee, float* out, int64_t ldo,
+                                 float beta, float* stat_m, float* stat_l, hipStream_t st);
+hipError_t dot_attn_edge_bwd_dst_f32(IType it, const int64_t* rowptr, const void* col,
+                                     int64_t nrows, int C, int heads, int64_t lds, float scale,
+                                     const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                     const float* v, int64_t ldv, const float* k2,
+                                     int64_t ldk2, const float* v2, int64_t ldv2,
+                                     int64_t nsplit, const float* ee, int64_t ldee,
+                                     const float* stat_m, const float* stat_l, const float* g,
+                                     int64_t ldg, const float* c, float* dq, int64_t lddq,
+                                     float* dee, int64_t lddee, float* w, int64_t ldw,
+                                     hipStream_t st);
+// rows = source rows; col = destination ids (q, g rows); t_slot = forward slots (w rows)
+hipError_t dot_attn_edge_bwd_src_f32(IType it, const int64_t* rowptr, const void* col,
+                                     const void* t_slot, int64_t nrows, int C, int heads,
+                                     float scale, const float* q, int64_t ldq, const float* g,
+                                     int64_t ldg, const float* w, int64_t ldw, float* dk,
+                                     int64_t lddk, float* dv, int64_t lddv, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // Fused fp32 GATv2 graph attention of one relation (gatv2_f32.hip):
 // e_ij = <a, LeakyReLU(xd_i + xs_j)> per head, softmax over each destination row's edges, the
 // weighted gather of xs_j, and the exact adjoint (destination side: dxd and the partial rows

@@ -127,6 +127,21 @@ def build_relation_graph(edges: torch.Tensor, src_type: int, dst_type: int,
     return RelationGraph(src_type, dst_type, cp, csr, Ld, Ls)
 
 
+def relation_edge_order(edges: torch.Tensor, offsets: Dict[int, torch.Tensor], dst_type: int,
+                        rank: int) -> torch.Tensor:
+    """For each CSR slot of the :class:`RelationGraph` that :func:`build_relation_graph`
+    builds on ``rank`` from the same ``edges[2, E]``, the column of ``edges`` the slot came
+    from (``LongTensor[E_local]``): this rank's edges (destination owned by it) in input
+    order, stably sorted by local destination — what ``CSR.from_coo`` does with the
+    pattern's local edge list. Per-edge attributes of the relation go to the rank as
+    ``edge_attr_global[order]``. No communication."""
+    off = offsets[dst_type]
+    lo, hi = int(off[rank]), int(off[rank + 1])
+    dst = edges[1].long()
+    mine = torch.nonzero((dst >= lo) & (dst < hi)).reshape(-1)
+    return mine[torch.sort(dst[mine], stable=True).indices]
+
+
 # ----------------------------------------------------------------------------- synthetic MAG
 def _generator(seed: int) -> torch.Generator:
     return torch.Generator().manual_seed(int(seed))

@@ -24,14 +24,24 @@ MI355X formulation (with a :class:`~dgraph_amd.data.hetero.RelationGraph`):
   gradient is computed first and returns to its owners under ``dq`` and the local ``dk`` /
   ``dv``. Still one exchange forward and one backward on every rank. The default is the
   synchronous exchange: the overlapped path has only been timed against a link model on
-  one GPU (PERFORMANCE.md), not on a multi-GPU node.
+  one GPU (PERFORMANCE.md), not on a multi-GPU node;
+* ``edge_dim=`` (PyG's ``edge_dim``, the UniMP edge term): ``edge_attr [E_local, edge_dim]``
+  in the relation's CSR slot order (:func:`~dgraph_amd.data.hetero.relation_edge_order`
+  gives that order for a global edge list) is projected by ``lin_edge`` (no bias) to
+  ``[E_local, C]`` and added to the edge's key and to its value inside the attention kernels
+  (``dot_attention(..., edge=)``, csrc/kernels/dot_attn_edge_f32.hip). Edge features live
+  with the destination's rank and never travel: still one exchange forward and one backward.
 
 Out of scope here: the same overlap for the GAT and GATv2 layers (their kernels have no carry-in
-forward yet); wiring the layer into ``CommAwareRGAT``, the lean ``HeteroGraph`` path or
-the OGB-LSC trainer; bf16; edge features; PyG's ``beta`` gate between the skip and the
-attention output; attention dropout.
+forward yet); edge features together with ``overlap=True`` (the carry-in forward and the
+parts / halo ops take none), in the GAT / GATv2 layers, or projected from ``edge_dim``
+columns inside the kernel (which would avoid the ``[E, C]`` tensor); wiring the layer into
+``CommAwareRGAT``, the lean ``HeteroGraph`` path, GraphCast or the OGB-LSC trainer; bf16;
+PyG's ``beta`` gate between the skip and the attention output; attention dropout.
 """
 from __future__ import annotations
+
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -44,10 +54,13 @@ from .rgat import _world
 class CommAwareTransformerConv(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, comm=None, heads: int = 1,
                  bias: bool = True, root_weight: bool = True, hetero: bool = False,
-                 overlap: bool = False):
+                 overlap: bool = False, edge_dim: Optional[int] = None):
         super().__init__()
         if out_channels % heads:
             raise ValueError("out_channels must be divisible by heads")
+        if edge_dim is not None and overlap:
+            raise ValueError("edge_dim with overlap=True is not supported: the overlapped "
+                             "attention op takes no edge features")
         self.comm = comm
         self.heads = heads
         self.hetero = hetero
@@ -55,6 +68,9 @@ class CommAwareTransformerConv(nn.Module):
         self.out_channels = out_channels
         self.lin_query = nn.Linear(in_channels, out_channels)
         self.lin_kv = nn.Linear(in_channels, 2 * out_channels)  # rows [W_k ; W_v]
+        self.edge_dim = edge_dim
+        if edge_dim is not None:  # (no attribute at all otherwise: state_dict keys as before)
+            self.lin_edge = nn.Linear(edge_dim, out_channels, bias=False)
         if root_weight:
             self.lin_skip = nn.Linear(in_channels, out_channels, bias=False)
         else:
@@ -75,8 +91,11 @@ class CommAwareTransformerConv(nn.Module):
             graph._cache["dot_attn_pattern"] = pat
         return pat
 
-    def forward(self, x, graph, x_j=None):
+    def forward(self, x, graph, x_j=None, edge_attr=None):
         C = self.out_channels
+        if (edge_attr is None) != (self.edge_dim is None):
+            raise ValueError("edge_attr is given exactly when the layer has edge_dim")
+        edge = None if edge_attr is None else self.lin_edge(edge_attr)
         q = self.lin_query(x)
         kv = self.lin_kv(x_j if (self.hetero and x_j is not None) else x)
         pat = self._pattern(graph)
@@ -95,7 +114,11 @@ class CommAwareTransformerConv(nn.Module):
                     self._halo = HaloExchange(self.comm)
                 halo = self._halo(kv, graph.pattern)
                 kh, vh = halo[:, :C], halo[:, C:]
-            out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads)
+            if edge is None:
+                out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads)
+            else:
+                out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads,
+                                    edge=edge)
         if self.lin_skip is not None:
             out = out + self.lin_skip(x)
         if self.bias is not None:

@@ -19,6 +19,13 @@ backward's ``c_i = <g_i, out_i>`` per head is one elementwise pass over the save
 Anything else on the GPU raises ``ValueError``. CPU: the same math in plain PyTorch
 autograd at fp64 (the numerics oracle), returned in the input dtype.
 
+With ``edge=`` (``[E, C]``, one row per CSR slot, added to the edge's key and value) the op
+runs the three kernels of csrc/kernels/dot_attn_edge_f32.hip instead: the forward and the
+destination side stream the edge rows in slot order, the destination side writes the per-edge
+gradient and two weights per slot and head, and the source side reads those weights through
+``GatPattern.t_slot``. :func:`dot_attention_parts` / :func:`dot_attention_halo` take no edge
+features.
+
 The forward can also start from an earlier pass's softmax state (``dot_attn_fwd_carry_f32``),
 which gives one softmax over a union of edge sets, one set per launch:
 :func:`dot_attention_parts` attends over several edge sets that have their own q / k / v, and
@@ -43,8 +50,9 @@ def shape_ok(C: int, heads: int) -> bool:
     return C in (64, 128, 256) and heads in (1, 2, 4, 8) and (C // 4) // heads >= 2
 
 
-def _reference(q, k, v, kh, vh, pat: GatPattern, heads: int, scale: float):
-    """The relation's attention output [R, C], differentiable plain PyTorch."""
+def _reference(q, k, v, kh, vh, pat: GatPattern, heads: int, scale: float, edge=None):
+    """The relation's attention output [R, C], differentiable plain PyTorch. ``edge`` [E, C]
+    (one row per CSR slot) is added to the gathered key and value rows."""
     R, C = pat.R, q.shape[1]
     D = C // heads
     ka = k if kh is None else torch.cat([k[:pat.nsplit], kh], 0)
@@ -53,13 +61,16 @@ def _reference(q, k, v, kh, vh, pat: GatPattern, heads: int, scale: float):
     cols = pat.col.long().to(q.device)
     rows = torch.repeat_interleave(torch.arange(R, device=q.device), rowptr[1:] - rowptr[:-1])
     E = rows.numel()
-    e = (q[rows].view(E, heads, D) * ka[cols].view(E, heads, D)).sum(-1) * scale
+    ke, ve = ka[cols], va[cols]
+    if edge is not None:
+        ke, ve = ke + edge, ve + edge
+    e = (q[rows].view(E, heads, D) * ke.view(E, heads, D)).sum(-1) * scale
     m = torch.full((R, heads), -float("inf"), dtype=e.dtype, device=q.device).index_reduce(
         0, rows, e.detach(), "amax", include_self=True)
     p = torch.exp(e - m[rows])
     den = torch.zeros(R, heads, dtype=e.dtype, device=q.device).index_add(0, rows, p)
     alpha = p / den[rows]
-    msg = (va[cols].view(E, heads, D) * alpha.unsqueeze(-1)).reshape(E, C)
+    msg = (ve.view(E, heads, D) * alpha.unsqueeze(-1)).reshape(E, C)
     return torch.zeros(R, C, dtype=q.dtype, device=q.device).index_add(0, rows, msg)
 
 
@@ -119,14 +130,72 @@ class _DotAttnFn(Function):
         return dq, dk, dv, dkh, dvh, None, None, None
 
 
+class _DotAttnEdgeFn(Function):
+    """The attention with ``edge`` added to key and value (dot_attn_edge_f32.hip). The
+    destination side of the backward also writes the per-edge gradient and the per-slot
+    weights ``w``, which the source side reads through ``pat.t_slot`` instead of recomputing
+    them."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, kh, vh, edge, pat: GatPattern, heads: int, scale: float):
+        ops = _native.ops()
+        q, k, v, kh, vh, edge = (_rows(t) for t in (q, k, v, kh, vh, edge))
+        R, C = pat.R, q.shape[1]
+        out = torch.empty(R, C, dtype=torch.float32, device=q.device)
+        m = torch.empty(R, heads, dtype=torch.float32, device=q.device)
+        l = torch.empty_like(m)
+        ops.dot_attn_edge_fwd_f32(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, edge, out,
+                                  0.0, m, l, heads, scale)
+        ctx.pat, ctx.heads, ctx.scale = pat, heads, scale
+        ctx.save_for_backward(q, k, v, kh, vh, edge, out, m, l)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, kh, vh, edge, out, m, l = ctx.saved_tensors
+        pat, Hh, scale = ctx.pat, ctx.heads, ctx.scale
+        ops = _native.ops()
+        R, C = out.shape
+        E = pat.col.numel()
+        g = _rows(g)
+        c = (g * out).reshape(R, Hh, C // Hh).sum(-1)
+        dq = torch.empty_like(out)
+        # every slot has exactly one writer (the pattern's rows cover all of its entries)
+        dee = torch.empty(E, C, dtype=torch.float32, device=g.device)
+        w = torch.empty(E, 2 * Hh, dtype=torch.float32, device=g.device)
+        ops.dot_attn_edge_bwd_dst_f32(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, edge,
+                                      m, l, g, c, dq, dee, w, Hh, scale)
+        # the source side: the local rows, then the halo rows over the tail of the transposed
+        # row pointer; rows past the pattern's columns have no entries
+        nloc = pat.nsplit if kh is not None else pat.nsplit + pat.H
+        alloc = torch.empty if k.shape[0] == nloc else torch.zeros
+        dk = alloc(k.shape[0], C, dtype=torch.float32, device=g.device)
+        dv = alloc(k.shape[0], C, dtype=torch.float32, device=g.device)
+        ops.dot_attn_edge_bwd_src_f32(pat.t_rowptr[:nloc + 1], pat.t_col, pat.t_slot, q, g, w,
+                                      dk, dv, Hh, scale)
+        dkh = dvh = None
+        if kh is not None:
+            alloc = torch.empty if kh.shape[0] == pat.H else torch.zeros
+            dkh = alloc(kh.shape[0], C, dtype=torch.float32, device=g.device)
+            dvh = alloc(kh.shape[0], C, dtype=torch.float32, device=g.device)
+            ops.dot_attn_edge_bwd_src_f32(pat.t_rowptr[pat.nsplit:], pat.t_col, pat.t_slot, q,
+                                          g, w, dkh, dvh, Hh, scale)
+        return dq, dk, dv, dkh, dvh, dee, None, None, None
+
+
 def dot_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pat: GatPattern,
                   kh: Optional[torch.Tensor] = None, vh: Optional[torch.Tensor] = None,
-                  scale: Optional[float] = None, *, heads: int = 1) -> torch.Tensor:
+                  scale: Optional[float] = None, *, heads: int = 1,
+                  edge: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``out[R, C]`` of the scaled dot-product attention of ``q [R, C]`` over ``pat``
     (autograd). Columns below ``pat.nsplit`` read ``k`` / ``v``, the others row
     ``column - pat.nsplit`` of ``kh`` / ``vh`` (without them: ``k`` / ``v`` hold every
     column's row). ``heads`` is a keyword argument (the tensors stay 2-D, heads are
-    contiguous column blocks); ``scale`` defaults to ``1 / sqrt(C / heads)``."""
+    contiguous column blocks); ``scale`` defaults to ``1 / sqrt(C / heads)``.
+
+    ``edge [E, C]`` (fp32 on the GPU): one row per CSR slot of ``pat`` (the order of
+    ``pat.col``), added to the edge's key and to its value (PyG's ``TransformerConv`` with
+    ``edge_dim``); its gradient is returned like any other. Without it nothing changes."""
     heads = int(heads)
     if q.dim() != 2 or k.dim() != 2 or k.shape != v.shape or k.shape[1] != q.shape[1]:
         raise ValueError("dot_attention: q [R, C] and k, v [N, C] expected")
@@ -144,18 +213,30 @@ def dot_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pat: GatPat
             kh.shape[1] != C:
         raise ValueError("dot_attention: k / v must have pat.nsplit rows and kh / vh the "
                          "pattern's halo rows")
+    if edge is not None and (edge.dim() != 2 or edge.shape[0] != pat.col.numel() or
+                             edge.shape[1] != C):
+        raise ValueError(f"dot_attention: edge must be [{pat.col.numel()}, {C}] (one row per "
+                         f"entry of the pattern), got {tuple(edge.shape)}")
     if scale is None:
         scale = 1.0 / math.sqrt(C // heads)
     scale = float(scale)
     if not q.is_cuda:
         dt = q.dtype
         up = lambda t: None if t is None else t.double()  # noqa: E731
-        return _reference(up(q), up(k), up(v), up(kh), up(vh), pat, heads, scale).to(dt)
+        if edge is None:
+            return _reference(up(q), up(k), up(v), up(kh), up(vh), pat, heads, scale).to(dt)
+        return _reference(up(q), up(k), up(v), up(kh), up(vh), pat, heads, scale,
+                          up(edge)).to(dt)
     if any(t is not None and t.dtype != torch.float32 for t in (q, k, v, kh, vh)) or \
             not shape_ok(C, heads):
         raise ValueError(f"dot_attention: unsupported on the GPU: dtype {q.dtype}, C = {C}, "
                          f"heads = {heads} (supported: {SUPPORTED})")
-    return _DotAttnFn.apply(q, k, v, kh, vh, pat, heads, scale)
+    if edge is None:
+        return _DotAttnFn.apply(q, k, v, kh, vh, pat, heads, scale)
+    if edge.dtype != torch.float32:
+        raise ValueError(f"dot_attention: unsupported on the GPU: edge dtype {edge.dtype} "
+                         f"(supported: {SUPPORTED})")
+    return _DotAttnEdgeFn.apply(q, k, v, kh, vh, edge, pat, heads, scale)
 
 
 # ------------------------------------------------------- one softmax over several edge sets

@@ -73,6 +73,17 @@ class GatPattern:
         self.t_rowptr = t.rowptr.long().contiguous()
         self.t_col = t.col.to(torch.int32).contiguous()
         self._split = None
+        self._t_slot = None
+
+    @property
+    def t_slot(self) -> torch.Tensor:
+        """The forward CSR slot of each entry of the transposed pattern (int32, the order of
+        ``t_col``: a stable sort of ``col``), so ``col[t_slot]`` is the entry's source row and
+        per-slot arrays can be read from the source side. Built on first use and kept."""
+        if self._t_slot is None:
+            perm = torch.sort(self.col.long(), stable=True).indices
+            self._t_slot = perm.to(torch.int32).contiguous()
+        return self._t_slot
 
     def split(self):
         """``(interior, halo)``: two one-source patterns over the same ``R`` rows, each with
