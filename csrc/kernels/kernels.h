@@ -513,6 +513,44 @@ hipError_t dot_attn_edge_bwd_src_f32(IType it, const int64_t* rowptr, const void
                                      int64_t lddk, float* dv, int64_t lddv, hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// The same attention with dropout on the attention coefficients (dot_attn_drop_f32.hip; PyG's
+// TransformerConv(dropout=p) in training), applied after the softmax: mm = keep / (1 - p)
+// with keep(slot, head) the Philox4x32-10 decision of philox.h, out = sum alpha mm v,
+// de = alpha (mm ga - c), dv = sum alpha mm g. stat_m / stat_l are the plain forward's. The
+// mask is never stored: every kernel regenerates it from (*seed, CSR slot, head); the source
+// side finds the slot of transposed entry p' at t_slot[p'] (col's index type, indexed by
+// absolute position, as col is). seed points to ONE int64 in device memory (read by the
+// kernels, so a captured step can refresh it per replay); thr = floor(p 2^32);
+// inv_keep = 1 / (1 - p). No beta and no carry. Launch conditions as dot_attn_*_f32.
+hipError_t dot_attn_drop_fwd_f32(IType it, const int64_t* rowptr, const void* col,
+                                 int64_t nrows, int C, int heads, int64_t lds, float scale,
+                                 const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                 const float* v, int64_t ldv, const float* k2, int64_t ldk2,
+                                 const float* v2, int64_t ldv2, int64_t nsplit, float* out,
+                                 int64_t ldo, float* stat_m, float* stat_l,
+                                 const int64_t* seed, uint32_t thr, float inv_keep,
+                                 hipStream_t st);
+hipError_t dot_attn_drop_bwd_dst_f32(IType it, const int64_t* rowptr, const void* col,
+                                     int64_t nrows, int C, int heads, int64_t lds, float scale,
+                                     const float* q, int64_t ldq, const float* k, int64_t ldk,
+                                     const float* v, int64_t ldv, const float* k2,
+                                     int64_t ldk2, const float* v2, int64_t ldv2,
+                                     int64_t nsplit, const float* stat_m, const float* stat_l,
+                                     const float* g, int64_t ldg, const float* c, float* dq,
+                                     int64_t lddq, const int64_t* seed, uint32_t thr,
+                                     float inv_keep, hipStream_t st);
+// rows = source rows (k / v resident); col = destination ids; t_slot = forward slots
+hipError_t dot_attn_drop_bwd_src_f32(IType it, const int64_t* rowptr, const void* col,
+                                     const void* t_slot, int64_t nrows, int C, int heads,
+                                     int64_t lds, float scale, const float* q, int64_t ldq,
+                                     const float* g, int64_t ldg, const float* k, int64_t ldk,
+                                     const float* v, int64_t ldv, const float* stat_m,
+                                     const float* stat_l, const float* c, float* dk,
+                                     int64_t lddk, float* dv, int64_t lddv,
+                                     const int64_t* seed, uint32_t thr, float inv_keep,
+                                     hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // Fused fp32 GATv2 graph attention of one relation (gatv2_f32.hip):
 // e_ij = <a, LeakyReLU(xd_i + xs_j)> per head, softmax over each destination row's edges, the
 // weighted gather of xs_j, and the exact adjoint (destination side: dxd and the partial rows

@@ -30,14 +30,24 @@ MI355X formulation (with a :class:`~dgraph_amd.data.hetero.RelationGraph`):
   gives that order for a global edge list) is projected by ``lin_edge`` (no bias) to
   ``[E_local, C]`` and added to the edge's key and to its value inside the attention kernels
   (``dot_attention(..., edge=)``, csrc/kernels/dot_attn_edge_f32.hip). Edge features live
-  with the destination's rank and never travel: still one exchange forward and one backward.
+  with the destination's rank and never travel: still one exchange forward and one backward;
+* ``dropout=`` (PyG's ``dropout``, as UniMP trains): in training the attention coefficients are
+  dropped after the softmax inside the kernels (``dot_attention(..., dropout_p=)``,
+  csrc/kernels/dot_attn_drop_f32.hip). No mask is stored: the keep decision of an edge is a
+  stateless function of a per-call seed, the edge's CSR slot and the head. The layer draws
+  the seed from the device's torch generator (no host sync) and, with more than one rank,
+  offsets it per rank, so equal torch seeds on all ranks do not give edges with equal local
+  slot numbers the same bits. ``forward(..., dropout_seed=)`` fixes the seed (tests, captured
+  steps). Evaluation mode and ``dropout=0`` are exactly the layer without it.
 
 Out of scope here: the same overlap for the GAT and GATv2 layers (their kernels have no carry-in
 forward yet); edge features together with ``overlap=True`` (the carry-in forward and the
 parts / halo ops take none), in the GAT / GATv2 layers, or projected from ``edge_dim``
 columns inside the kernel (which would avoid the ``[E, C]`` tensor); wiring the layer into
 ``CommAwareRGAT``, the lean ``HeteroGraph`` path, GraphCast or the OGB-LSC trainer; bf16;
-PyG's ``beta`` gate between the skip and the attention output; attention dropout.
+PyG's ``beta`` gate between the skip and the attention output; attention dropout together
+with ``overlap=True`` or ``edge_dim`` (the carry-in forward, the parts / halo ops and the
+edge-feature kernels take none) or in the GAT / GATv2 layers; a fused feature-dropout epilogue.
 """
 from __future__ import annotations
 
@@ -54,10 +64,18 @@ from .rgat import _world
 class CommAwareTransformerConv(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, comm=None, heads: int = 1,
                  bias: bool = True, root_weight: bool = True, hetero: bool = False,
-                 overlap: bool = False, edge_dim: Optional[int] = None):
+                 overlap: bool = False, edge_dim: Optional[int] = None, dropout: float = 0.0):
         super().__init__()
         if out_channels % heads:
             raise ValueError("out_channels must be divisible by heads")
+        dropout = float(dropout)
+        if not 0.0 <= dropout < 1.0:
+            raise ValueError(f"dropout must lie in [0, 1), got {dropout}")
+        if dropout > 0.0 and (overlap or edge_dim is not None):
+            raise ValueError("dropout with overlap=True or edge_dim is not supported: the "
+                             "overlapped attention op and the edge-feature kernels take no "
+                             "attention dropout")
+        self.dropout = dropout
         if edge_dim is not None and overlap:
             raise ValueError("edge_dim with overlap=True is not supported: the overlapped "
                              "attention op takes no edge features")
@@ -91,7 +109,18 @@ class CommAwareTransformerConv(nn.Module):
             graph._cache["dot_attn_pattern"] = pat
         return pat
 
-    def forward(self, x, graph, x_j=None, edge_attr=None):
+    _RANK_MIX = 0x9E3779B97F4A7C15  # per-rank seed offset (mod 2^62): the 64-bit golden ratio
+
+    def _dropout_seed(self, device, dropout_seed=None) -> torch.Tensor:
+        """This call's seed tensor: the given one, or one drawn from ``device``'s torch
+        generator, plus the rank's offset (a tensor add, no sync)."""
+        if dropout_seed is None:
+            dropout_seed = torch.randint(0, 2 ** 62, (1,), device=device)
+        if _world(self.comm) > 1:
+            dropout_seed = dropout_seed + (self.comm.get_rank() * self._RANK_MIX) % 2 ** 62
+        return dropout_seed
+
+    def forward(self, x, graph, x_j=None, edge_attr=None, dropout_seed=None):
         C = self.out_channels
         if (edge_attr is None) != (self.edge_dim is None):
             raise ValueError("edge_attr is given exactly when the layer has edge_dim")
@@ -114,7 +143,11 @@ class CommAwareTransformerConv(nn.Module):
                     self._halo = HaloExchange(self.comm)
                 halo = self._halo(kv, graph.pattern)
                 kh, vh = halo[:, :C], halo[:, C:]
-            if edge is None:
+            if self.training and self.dropout > 0.0:
+                out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads,
+                                    dropout_p=self.dropout,
+                                    dropout_seed=self._dropout_seed(q.device, dropout_seed))
+            elif edge is None:
                 out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads)
             else:
                 out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads,

@@ -26,6 +26,18 @@ gradient and two weights per slot and head, and the source side reads those weig
 ``GatPattern.t_slot``. :func:`dot_attention_parts` / :func:`dot_attention_halo` take no edge
 features.
 
+With ``dropout_p > 0`` (PyG's ``TransformerConv(dropout=p)`` in training) the attention
+coefficients are dropped after the softmax: ``out_i = sum_j alpha_ij keep_ij / (1 - p) v_j``
+with ``alpha`` the softmax over ALL edges of the row. The keep decision of an edge is a
+stateless function of ``(seed, CSR slot, head)`` (Philox4x32-10, ``ops/philox.py`` and
+``csrc/kernels/philox.h``), so the three kernels of csrc/kernels/dot_attn_drop_f32.hip
+regenerate the same mask with none stored (the source side through ``GatPattern.t_slot``) and
+the CPU path regenerates it bit for bit. The seed is a 1-element int64 tensor that the kernels
+read from device memory: a captured step gets a fresh mask per replay when the caller rewrites
+it. Out of scope: dropout together with ``edge=``, in :func:`dot_attention_parts` /
+:func:`dot_attention_halo` (the carry forward), in the GAT / GATv2 ops (``philox.h`` is
+written so that they can adopt it), in bf16, and a fused feature-dropout epilogue.
+
 The forward can also start from an earlier pass's softmax state (``dot_attn_fwd_carry_f32``),
 which gives one softmax over a union of edge sets, one set per launch:
 :func:`dot_attention_parts` attends over several edge sets that have their own q / k / v, and
@@ -50,9 +62,12 @@ def shape_ok(C: int, heads: int) -> bool:
     return C in (64, 128, 256) and heads in (1, 2, 4, 8) and (C // 4) // heads >= 2
 
 
-def _reference(q, k, v, kh, vh, pat: GatPattern, heads: int, scale: float, edge=None):
+def _reference(q, k, v, kh, vh, pat: GatPattern, heads: int, scale: float, edge=None,
+               keep=None, dropout_p: float = 0.0):
     """The relation's attention output [R, C], differentiable plain PyTorch. ``edge`` [E, C]
-    (one row per CSR slot) is added to the gathered key and value rows."""
+    (one row per CSR slot) is added to the gathered key and value rows; ``keep`` [E, heads]
+    (bool, one row per CSR slot) drops coefficients after the normalisation, the kept ones
+    scaled by ``1 / (1 - dropout_p)``."""
     R, C = pat.R, q.shape[1]
     D = C // heads
     ka = k if kh is None else torch.cat([k[:pat.nsplit], kh], 0)
@@ -70,6 +85,8 @@ def _reference(q, k, v, kh, vh, pat: GatPattern, heads: int, scale: float, edge=
     p = torch.exp(e - m[rows])
     den = torch.zeros(R, heads, dtype=e.dtype, device=q.device).index_add(0, rows, p)
     alpha = p / den[rows]
+    if keep is not None:
+        alpha = alpha * (keep.to(alpha.dtype) / (1.0 - dropout_p))
     msg = (ve.view(E, heads, D) * alpha.unsqueeze(-1)).reshape(E, C)
     return torch.zeros(R, C, dtype=q.dtype, device=q.device).index_add(0, rows, msg)
 
@@ -183,10 +200,61 @@ class _DotAttnEdgeFn(Function):
         return dq, dk, dv, dkh, dvh, dee, None, None, None
 
 
+class _DotAttnDropFn(Function):
+    """The attention with dropout on the coefficients (dot_attn_drop_f32.hip). No mask is
+    saved: the seed tensor is, and the backward kernels regenerate the forward's bits from it
+    (the source side through ``pat.t_slot``)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, kh, vh, seed, pat: GatPattern, heads: int, scale: float,
+                p: float):
+        ops = _native.ops()
+        q, k, v, kh, vh = (_rows(t) for t in (q, k, v, kh, vh))
+        R, C = pat.R, q.shape[1]
+        out = torch.empty(R, C, dtype=torch.float32, device=q.device)
+        m = torch.empty(R, heads, dtype=torch.float32, device=q.device)
+        l = torch.empty_like(m)
+        ops.dot_attn_drop_fwd_f32(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, out, m, l,
+                                  seed, p, heads, scale)
+        ctx.pat, ctx.heads, ctx.scale, ctx.p = pat, heads, scale, p
+        ctx.save_for_backward(q, k, v, kh, vh, seed, out, m, l)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, kh, vh, seed, out, m, l = ctx.saved_tensors
+        pat, Hh, scale, p = ctx.pat, ctx.heads, ctx.scale, ctx.p
+        ops = _native.ops()
+        R, C = out.shape
+        g = _rows(g)
+        # c_i^h = <g_i^h, o_i^h> = sum_j alpha_ij m'_ij <g_i^h, v_j^h>: still the saved output's
+        c = (g * out).reshape(R, Hh, C // Hh).sum(-1)
+        dq = torch.empty_like(out)
+        ops.dot_attn_drop_bwd_dst_f32(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, m, l, g,
+                                      c, dq, seed, p, Hh, scale)
+        # the source side: the local rows, then the halo rows over the tail of the transposed
+        # row pointer; rows past the pattern's columns have no entries
+        nloc = pat.nsplit if kh is not None else pat.nsplit + pat.H
+        alloc = torch.empty if k.shape[0] == nloc else torch.zeros
+        dk = alloc(k.shape[0], C, dtype=torch.float32, device=g.device)
+        dv = alloc(k.shape[0], C, dtype=torch.float32, device=g.device)
+        ops.dot_attn_drop_bwd_src_f32(pat.t_rowptr[:nloc + 1], pat.t_col, pat.t_slot, q, g, k,
+                                      v, m, l, c, dk, dv, seed, p, Hh, scale)
+        dkh = dvh = None
+        if kh is not None:
+            alloc = torch.empty if kh.shape[0] == pat.H else torch.zeros
+            dkh = alloc(kh.shape[0], C, dtype=torch.float32, device=g.device)
+            dvh = alloc(kh.shape[0], C, dtype=torch.float32, device=g.device)
+            ops.dot_attn_drop_bwd_src_f32(pat.t_rowptr[pat.nsplit:], pat.t_col, pat.t_slot, q,
+                                          g, kh, vh, m, l, c, dkh, dvh, seed, p, Hh, scale)
+        return dq, dk, dv, dkh, dvh, None, None, None, None, None
+
+
 def dot_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pat: GatPattern,
                   kh: Optional[torch.Tensor] = None, vh: Optional[torch.Tensor] = None,
                   scale: Optional[float] = None, *, heads: int = 1,
-                  edge: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  edge: Optional[torch.Tensor] = None, dropout_p: float = 0.0,
+                  dropout_seed: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``out[R, C]`` of the scaled dot-product attention of ``q [R, C]`` over ``pat``
     (autograd). Columns below ``pat.nsplit`` read ``k`` / ``v``, the others row
     ``column - pat.nsplit`` of ``kh`` / ``vh`` (without them: ``k`` / ``v`` hold every
@@ -195,8 +263,20 @@ def dot_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pat: GatPat
 
     ``edge [E, C]`` (fp32 on the GPU): one row per CSR slot of ``pat`` (the order of
     ``pat.col``), added to the edge's key and to its value (PyG's ``TransformerConv`` with
-    ``edge_dim``); its gradient is returned like any other. Without it nothing changes."""
+    ``edge_dim``); its gradient is returned like any other. Without it nothing changes.
+
+    ``dropout_p`` in ``(0, 1)``: dropout on the attention coefficients, after the softmax
+    (the module docstring). ``dropout_seed``: a 1-element int64 tensor on ``q``'s device that
+    fixes the mask; ``None`` draws one from the device's torch generator (reproducible under
+    ``torch.manual_seed``, no host sync). ``dropout_p = 0`` (the default) is exactly the call
+    without the two arguments; the seed is then ignored. Not available with ``edge=``."""
     heads = int(heads)
+    dropout_p = float(dropout_p)
+    if not 0.0 <= dropout_p < 1.0:
+        raise ValueError(f"dot_attention: dropout_p must lie in [0, 1), got {dropout_p}")
+    if dropout_p > 0.0 and edge is not None:
+        raise ValueError("dot_attention: dropout_p > 0 together with edge= is not supported "
+                         "(the edge-feature kernels take no dropout)")
     if q.dim() != 2 or k.dim() != 2 or k.shape != v.shape or k.shape[1] != q.shape[1]:
         raise ValueError("dot_attention: q [R, C] and k, v [N, C] expected")
     C = q.shape[1]
@@ -220,9 +300,22 @@ def dot_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pat: GatPat
     if scale is None:
         scale = 1.0 / math.sqrt(C // heads)
     scale = float(scale)
+    if dropout_p > 0.0:
+        if dropout_seed is None:
+            dropout_seed = torch.randint(0, 2 ** 62, (1,), device=q.device)
+        elif not isinstance(dropout_seed, torch.Tensor) or dropout_seed.numel() != 1 or \
+                dropout_seed.dtype != torch.int64 or dropout_seed.device != q.device:
+            raise ValueError("dot_attention: dropout_seed must be a 1-element int64 tensor on "
+                             f"{q.device}")
     if not q.is_cuda:
         dt = q.dtype
         up = lambda t: None if t is None else t.double()  # noqa: E731
+        if dropout_p > 0.0:
+            from .philox import attn_keep_mask
+
+            keep = attn_keep_mask(dropout_seed, pat.col.numel(), heads, dropout_p)
+            return _reference(up(q), up(k), up(v), up(kh), up(vh), pat, heads, scale,
+                              keep=keep, dropout_p=dropout_p).to(dt)
         if edge is None:
             return _reference(up(q), up(k), up(v), up(kh), up(vh), pat, heads, scale).to(dt)
         return _reference(up(q), up(k), up(v), up(kh), up(vh), pat, heads, scale,
@@ -231,6 +324,9 @@ def dot_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pat: GatPat
             not shape_ok(C, heads):
         raise ValueError(f"dot_attention: unsupported on the GPU: dtype {q.dtype}, C = {C}, "
                          f"heads = {heads} (supported: {SUPPORTED})")
+    if dropout_p > 0.0:
+        return _DotAttnDropFn.apply(q, k, v, kh, vh, dropout_seed.reshape(1), pat, heads,
+                                    scale, dropout_p)
     if edge is None:
         return _DotAttnFn.apply(q, k, v, kh, vh, pat, heads, scale)
     if edge.dtype != torch.float32:
