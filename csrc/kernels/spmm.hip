@@ -40,7 +40,8 @@ __global__ __launch_bounds__(256) void spmm_csr_kernel(
     for (int fc = 0; fc < F; fc += LPR * VEC) {
       const int f = fc + l * VEC;
       const bool active = f < F;
-      const int h = (heads > 1) ? (f / head_dim) : 0;
+      // (inactive lanes read head 0: f / head_dim is past the last head there)
+      const int h = (heads > 1 && active) ? (f / head_dim) : 0;
       float acc[VEC];
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = 0.f;
@@ -146,7 +147,8 @@ __global__ __launch_bounds__(256) void spmm_csr_v2_kernel(
     for (int fc = 0; fc < F; fc += LPR * VEC) {
       const int f = fc + l * VEC;
       const bool active = f < F;
-      const int h = multi_head ? (f / head_dim) : 0;
+      // (inactive lanes read head 0: f / head_dim is past the last head there)
+      const int h = (multi_head && active) ? (f / head_dim) : 0;
       float acc[VEC];
 #pragma unroll
       for (int i = 0; i < VEC; ++i) acc[i] = 0.f;

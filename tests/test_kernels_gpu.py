@@ -92,9 +92,13 @@ def test_spmm_variants_agree_ragged_rows(variant, xcd, F):
     ops = _native.ops()
     try:
         ops.set_spmm_config(variant, xcd)
+        # (with it on, every fp32 width here runs the fp32 row-group kernel of
+        # spmm_f32.hip, whatever variant and xcd say)
+        ops.set_spmm_f32_config(0)
         out = K.spmm(rowptr.to(DEV), col.to(DEV), x)
     finally:
         ops.set_spmm_config(-1, -1)
+        ops.set_spmm_f32_config(1)
     torch.testing.assert_close(out.cpu(), ref, atol=1e-4, rtol=1e-4)
 
 
@@ -321,7 +325,7 @@ def test_pair_relu_modes(F, dtype, idx):
 
 @pytest.mark.parametrize("F", [3, 8, 64, 200])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("act", ["none", "relu", "silu"])
+@pytest.mark.parametrize("act", ["none", "relu", "silu", "leaky_relu"])
 def test_gather_add_act(F, dtype, act):
     E, Vs, Vd = 3000, 150, 170
     gen = torch.Generator().manual_seed(F)
