@@ -369,6 +369,14 @@ at::Tensor col_sum_op(const at::Tensor& g) {
   return partial.sum(0);
 }
 
+// a 256-thread block of bias_act holds one row at VEC columns per thread (kernels.h)
+void bias_act_check_width(DType dt, int64_t F, int vec) {
+  const int V = dt == DType::F32 ? 4 : 8;
+  TORCH_CHECK(F <= 256 * vec, "bias_act: feature width ", F, " exceeds the limit of ", 256 * vec,
+              " columns for these operands (", 256 * V, " when the width and every row stride "
+              "are multiples of ", V, " and every base is 16-byte aligned, 256 otherwise)");
+}
+
 // y = act(z + b) (act: 0 identity, 1 SiLU, 2 ReLU); z, y 2-D row-strided, b fp32 [F] or None
 void bias_act_op(const at::Tensor& z, const c10::optional<at::Tensor>& b, int64_t act,
                  const at::Tensor& y) {
@@ -379,6 +387,10 @@ void bias_act_op(const at::Tensor& z, const c10::optional<at::Tensor>& b, int64_
   TORCH_CHECK(z.sizes() == y.sizes() && z.scalar_type() == y.scalar_type(), "z / y mismatch");
   const float* bp = opt_f32(b, z, "b");
   if (bp) TORCH_CHECK(b->numel() == z.size(1) && b->is_contiguous(), "b must be [F]");
+  if (z.size(0) > 0)
+    bias_act_check_width(dtype_of(z), z.size(1),
+                         bias_act_vec(dtype_of(z), static_cast<int>(z.size(1)),
+                                      {z.stride(0), y.stride(0)}, {z.data_ptr(), y.data_ptr()}));
   c10::DeviceGuard gd(z.device());
   DG_HIP_CHECK(bias_act_fwd(dtype_of(z), static_cast<int>(act), z.data_ptr(), z.stride(0), bp,
                             y.data_ptr(), y.stride(0), z.size(0), static_cast<int>(z.size(1)),
@@ -400,6 +412,11 @@ at::Tensor bias_act_bwd_op(const at::Tensor& dy, const at::Tensor& z,
   const float* bp = opt_f32(b, z, "b");
   if (bp) TORCH_CHECK(b->numel() == z.size(1) && b->is_contiguous(), "b must be [F]");
   const int64_t L = z.size(0), F = z.size(1);
+  if (L > 0)
+    bias_act_check_width(dtype_of(z), F,
+                         bias_act_vec(dtype_of(z), static_cast<int>(F),
+                                      {dy.stride(0), z.stride(0), dz.stride(0)},
+                                      {dy.data_ptr(), z.data_ptr(), dz.data_ptr()}));
   const int64_t nb = std::max<int64_t>(1, std::min<int64_t>(1024, (L + 255) / 256));
   auto partial = at::empty({nb, F}, z.options().dtype(at::kFloat));
   c10::DeviceGuard gd(z.device());

@@ -134,23 +134,30 @@ inline bool a16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) ==
 
 }  // namespace
 
+int bias_act_vec(DType dt, int F, std::initializer_list<int64_t> lds,
+                 std::initializer_list<const void*> ptrs) {
+  const int V = dt == DType::F32 ? 4 : 8;
+  bool ok = F % V == 0 && F / V <= 256;
+  for (auto ld : lds) ok = ok && ld % V == 0;
+  for (auto p : ptrs) ok = ok && a16(p);
+  return ok ? V : 1;
+}
+
 hipError_t bias_act_fwd(DType dt, int act, const void* z, int64_t ldz, const float* b, void* y,
                         int64_t ldy, int64_t M, int F, hipStream_t st) {
   if (M <= 0 || F <= 0) return hipSuccess;
   if (act < 0 || act > 2) return hipErrorInvalidValue;
+  const int vec = bias_act_vec(dt, F, {ldz, ldy}, {z, y});
+  if (F > 256 * vec) return hipErrorInvalidValue;
   if (dt == DType::F32) {
     auto zp = static_cast<const float*>(z);
     auto yp = static_cast<float*>(y);
-    if (F % 4 == 0 && ldz % 4 == 0 && ldy % 4 == 0 && F / 4 <= 256 && a16(z) && a16(y))
-      return fwd_vec<float, 4>(act, zp, ldz, b, yp, ldy, M, F, st);
-    if (F > 256) return hipErrorInvalidValue;
+    if (vec == 4) return fwd_vec<float, 4>(act, zp, ldz, b, yp, ldy, M, F, st);
     return fwd_vec<float, 1>(act, zp, ldz, b, yp, ldy, M, F, st);
   }
   auto zp = static_cast<const uint16_t*>(z);
   auto yp = static_cast<uint16_t*>(y);
-  if (F % 8 == 0 && ldz % 8 == 0 && ldy % 8 == 0 && F / 8 <= 256 && a16(z) && a16(y))
-    return fwd_vec<uint16_t, 8>(act, zp, ldz, b, yp, ldy, M, F, st);
-  if (F > 256) return hipErrorInvalidValue;
+  if (vec == 8) return fwd_vec<uint16_t, 8>(act, zp, ldz, b, yp, ldy, M, F, st);
   return fwd_vec<uint16_t, 1>(act, zp, ldz, b, yp, ldy, M, F, st);
 }
 
@@ -159,23 +166,21 @@ hipError_t bias_act_bwd(DType dt, int act, const void* dy, int64_t lddy, const v
                         float* partial, int nblocks, hipStream_t st) {
   if (M <= 0 || F <= 0) return hipSuccess;
   if (act < 0 || act > 2 || nblocks <= 0) return hipErrorInvalidValue;
+  const int vec = bias_act_vec(dt, F, {lddy, ldz, lddz}, {dy, z, dz});
+  if (F > 256 * vec) return hipErrorInvalidValue;
   if (dt == DType::F32) {
     auto g = static_cast<const float*>(dy);
     auto zp = static_cast<const float*>(z);
     auto o = static_cast<float*>(dz);
-    if (F % 4 == 0 && lddy % 4 == 0 && ldz % 4 == 0 && lddz % 4 == 0 && F / 4 <= 256 &&
-        a16(dy) && a16(z) && a16(dz))
+    if (vec == 4)
       return bwd_vec<float, 4>(act, g, lddy, zp, ldz, b, o, lddz, M, F, partial, nblocks, st);
-    if (F > 256) return hipErrorInvalidValue;
     return bwd_vec<float, 1>(act, g, lddy, zp, ldz, b, o, lddz, M, F, partial, nblocks, st);
   }
   auto g = static_cast<const uint16_t*>(dy);
   auto zp = static_cast<const uint16_t*>(z);
   auto o = static_cast<uint16_t*>(dz);
-  if (F % 8 == 0 && lddy % 8 == 0 && ldz % 8 == 0 && lddz % 8 == 0 && F / 8 <= 256 &&
-      a16(dy) && a16(z) && a16(dz))
+  if (vec == 8)
     return bwd_vec<uint16_t, 8>(act, g, lddy, zp, ldz, b, o, lddz, M, F, partial, nblocks, st);
-  if (F > 256) return hipErrorInvalidValue;
   return bwd_vec<uint16_t, 1>(act, g, lddy, zp, ldz, b, o, lddz, M, F, partial, nblocks, st);
 }
 

@@ -8,6 +8,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 namespace dgraph {
 
 enum class DType : int { F32 = 0, BF16 = 1 };
@@ -260,7 +262,14 @@ hipError_t row_scale_colsum(const void* x, int64_t ldx, const float* s, void* ou
 hipError_t row_scale_cols(DType dt, const void* x, int64_t ldx, const float* s, void* out,
                           int64_t ldo, int64_t L, int w, hipStream_t stream);
 
-// fused bias + activation (act.hip): act 0 identity, 1 SiLU, 2 ReLU; F <= 256 (vector lanes)
+// fused bias + activation (act.hip): act 0 identity, 1 SiLU, 2 ReLU. One thread owns VEC
+// columns of a row and a 256-thread block must hold a whole row, so F <= 256 * VEC: the
+// 16-byte path (VEC = 4 fp32 / 8 bf16; F and every row stride a multiple of VEC, every
+// base 16-byte aligned) takes F <= 1024 fp32 / 2048 bf16, anything else runs with VEC = 1
+// and F <= 256. bias_act_vec returns the VEC the launchers take for a width, the row strides
+// and the base pointers of a call; F > 256 * VEC is hipErrorInvalidValue.
+int bias_act_vec(DType dt, int F, std::initializer_list<int64_t> lds,
+                 std::initializer_list<const void*> ptrs);
 hipError_t bias_act_fwd(DType dt, int act, const void* z, int64_t ldz, const float* b, void* y,
                         int64_t ldy, int64_t M, int F, hipStream_t st);
 hipError_t bias_act_bwd(DType dt, int act, const void* dy, int64_t lddy, const void* z,

@@ -62,7 +62,15 @@ __global__ __launch_bounds__(256) void layer_norm_fwd_kernel(
     }
 #pragma unroll
     for (int off = 1; off < LPR; off <<= 1) s += __shfl_xor(s, off, kWave);
-    const float mu = s * invF;
+    // a rounded product, not one the compiler may fuse into the ``v - mu`` below (HIP's
+    // __fmul_rn is a plain product and fuses too): fused, a constant row of 1000s got
+    // d = -3e-5 instead of 0 and, at rstd = eps^-1/2, y off by 0.03, and the forward
+    // normalised against another mean than the one it stores for the backward
+    float mu;
+    {
+#pragma clang fp contract(off)
+      mu = s * invF;
+    }
     float q = 0.f;
 #pragma unroll
     for (int c = 0; c < CH; ++c) {

@@ -213,11 +213,22 @@ class _SyncBNFn(Function):
         return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
+def dropout_threshold(p: float) -> int:
+    """The 32-bit keep threshold of a drop probability, exactly as ``set_dropout`` of
+    csrc/kernels/batchnorm.hip derives it: the kernels receive ``p`` as an fp32, so the
+    threshold is ``floor(float32(p) * 2^32)`` clamped to [1, 2^32 - 1] (0: no dropout).
+    With the Python double instead, p = 0.1 gave 429496729 here and 429496736 there."""
+    p32 = float(torch.tensor(float(p), dtype=torch.float32))
+    if not 0.0 < p32 < 1.0:
+        return 0
+    return min(max(int(p32 * 4294967296.0), 1), 0xFFFFFFFF)
+
+
 def dropout_keep_mask(seed: int, N: int, F: int, device=None, p: float = 0.0) -> torch.Tensor:
     """The fused-dropout keep mask of the native BN kernels (csrc/kernels/batchnorm.hip
     ``dropout_keep``): keep (r, c) iff fmix32 of the element index r * F + c mixed with the
-    64-bit seed is >= p * 2^32. A pure function of (seed, index): forward and backward (and
-    the CPU reference and the GPU kernels) agree bit for bit."""
+    64-bit seed is >= :func:`dropout_threshold` of ``p``. A pure function of (seed, index):
+    forward and backward (and the CPU reference and the GPU kernels) agree bit for bit."""
     M = 0xFFFFFFFF
     idx = torch.arange(N * F, dtype=torch.int64, device=device)
     lo, hi = idx & M, idx >> 32
@@ -228,8 +239,7 @@ def dropout_keep_mask(seed: int, N: int, F: int, device=None, p: float = 0.0) ->
     h = h ^ (h >> 13)
     h = (h * 0xC2B2AE35) & M
     h = h ^ (h >> 16)
-    t = min(max(int(p * 4294967296.0), 1), 0xFFFFFFFF) if p > 0 else 0
-    return (h >= t).view(N, F)
+    return (h >= dropout_threshold(p)).view(N, F)
 
 
 class DistributedBatchNorm1D(nn.Module):
