@@ -591,4 +591,25 @@ hipError_t gatv2_bwd_src_f32(IType it, const int64_t* rowptr, const void* col, i
                              const float* stat_l, const float* c, float* dxs, int64_t lddxs,
                              hipStream_t st);
 
+// ---------------------------------------------------------------------------
+// Per-edge dot products over a CSR pattern (SDDMM, sddmm.hip):
+//   s[k, h] = scale * row_scale[r(k)] * sum_{d < F / heads} a[r(k), h D + d] * b[col[k], h D + d]
+// for every slot k of the CSR, r(k) the row that holds it. a / b: fp32 or bf16 (dt), row
+// strides lda / ldb in elements; row_scale [nrows] or null (== 1); s: contiguous fp32
+// [nnz, heads]. fp32 accumulation in a fixed order, no atomics: bitwise reproducible and equal
+// for both index widths. rowptr[0] == 0, rowptr[nrows] == nnz and nrows < 2^31. Returns before
+// any launch when nnz, nrows or F is 0.
+//   sddmm_vec_shape_ok: the shape takes the 4-elements-per-lane path (D % 4 == 0, D / 4 a
+//   power of two, D <= 1024), which needs a / b bases aligned to 4 elements and lda, ldb
+//   divisible by 4; every other shape takes the element-per-lane path, which needs neither.
+//   sddmm_grid_cap: the most workgroups (of 4 waves) a launch uses; sddmm_chunk_slots: the
+//   slots a wave takes at a time, so one sweep of the grid is 4 cap chunk slots.
+bool sddmm_vec_shape_ok(int F, int heads);
+int64_t sddmm_grid_cap();
+int64_t sddmm_chunk_slots(int F, int heads);
+hipError_t sddmm_csr(DType dt, IType it, const int64_t* rowptr, const void* col, int64_t nrows,
+                     int64_t nnz, const void* a, int64_t lda, const void* b, int64_t ldb,
+                     int F, int heads, float scale, const float* row_scale, float* s,
+                     hipStream_t st);
+
 }  // namespace dgraph

@@ -10,4 +10,7 @@ def __getattr__(name):
     if name == "CommAwareGENConv":
         from .genconv import CommAwareGENConv
         return CommAwareGENConv
+    if name in ("InnerProductDecoder", "recon_loss", "negative_pattern"):
+        from . import link_pred
+        return getattr(link_pred, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -7,6 +7,9 @@ def __getattr__(name):
     if name in ("dot_attention_parts", "dot_attention_halo", "HaloPlan"):
         from . import dot_attn
         return getattr(dot_attn, name)
+    if name == "edge_dot":  # next to aggregate (ops/aggregate.py)
+        from .aggregate import edge_dot
+        return edge_dot
     if name == "gatv2_attention":
         from .gatv2 import gatv2_attention
         return gatv2_attention

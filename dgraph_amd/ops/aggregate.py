@@ -11,6 +11,8 @@
   (the core contract of the reference, tests/test_NCCLCommPlan.py:100-111,297-307),
   and both are deterministic (segment sums, no float atomics).
 * :func:`edge_softmax` — stable softmax over each destination's incoming edges.
+* :func:`edge_dot` — one dot product per CSR entry and head from two vertex rows (SDDMM);
+  backward is two edge-weighted SpMMs.
 """
 from __future__ import annotations
 
@@ -50,15 +52,18 @@ class _AggregateFn(Function):
                 gx = K.spmm(t.rowptr, t.col, g, edge_weight=ew_t, col_scale=col_scale,
                             heads=ctx.heads)
         if ew is not None and ctx.needs_input_grad[2]:
-            # d w[j,h] = row_scale[r] * <g[r, h-slice], x[c_j, h-slice]>  (SDDMM)
-            rows = csr.row_ids()
-            H = ctx.heads
-            cdt = torch.float64 if ew.dtype == torch.float64 else torch.float32
-            gr = g.to(cdt)[rows].view(csr.nnz, H, -1)
-            xc = x_saved.to(cdt)[csr.col.long()].view(csr.nnz, H, -1)
-            gw = (gr * xc).sum(-1)
-            if ctx.mean:
-                gw = gw * csr.inv_degree()[rows].unsqueeze(1)
+            # d w[j,h] = row_scale[r] * <g[r, h-slice], x[c_j, h-slice]>  (SDDMM): one
+            # kernel on the GPU (fp32 scores, nothing [nnz, F] is written); on the CPU the
+            # composed expression, in fp64 when the weights are
+            gg, xx = g, x_saved
+            if not g.is_cuda:
+                cdt = torch.float64 if ew.dtype == torch.float64 else torch.float32
+                gg, xx = g.to(cdt), x_saved.to(cdt)
+            else:  # a contiguous view off a 4-element boundary: the kernel's vector path
+                gg, xx = (t.clone() if t.data_ptr() % (4 * t.element_size()) else t
+                          for t in (g, x_saved))
+            gw = K.edge_dot(csr.rowptr, csr.col, gg, xx, heads=ctx.heads,
+                            row_scale=csr.inv_degree() if ctx.mean else None)
             gw = gw.reshape(ew.shape).to(ew.dtype)
         return gx, None, gw, None, None
 
@@ -272,6 +277,87 @@ def aggregate(
         if ew.dtype not in (torch.float32, torch.float64):
             ew = ew.float()
     return _AggregateFn.apply(x.contiguous(), csr, ew, reduce == "mean", heads)
+
+
+def _slot_transpose(csr: CSR) -> CSR:
+    """The transposed pattern WITH its slot map (``perm``: its slots as ``csr``'s slots). A
+    ``symmetric`` CSR's :meth:`CSR.transpose` is the pattern alone, so one is built (and
+    cached by :meth:`CSR.transpose_rel`)."""
+    t = csr.transpose()
+    if t is csr or not t._perm_to_parent or t._transpose is not csr:
+        t = csr.transpose_rel()[0]
+    return t
+
+
+def edge_dot_grads(csr: CSR, a, b, w, heads: int, want_a: bool = True, want_b: bool = True,
+                   da_out: Optional[torch.Tensor] = None, beta: float = 0.0):
+    """The adjoint of ``s = edge_dot(a, b)`` applied to ``w = scale * dL/ds`` (``[nnz,
+    heads]``), as two edge-weighted SpMMs: ``da[r] = sum_k w_k b[col[k]]`` over ``csr`` (into
+    ``da_out`` with ``beta`` when given) and ``db[c] = sum_k w_k a[r(k)]`` over its transpose
+    (``[csr.num_cols, F]``)."""
+    da = db = None
+    if want_a:
+        da = K.spmm(csr.rowptr, csr.col, b, da_out, edge_weight=w, heads=heads, beta=beta)
+    if want_b:
+        t = _slot_transpose(csr)
+        db = K.spmm(t.rowptr, t.col, a, edge_weight=w[t.perm].contiguous(), heads=heads)
+    return da, db
+
+
+class _EdgeDotFn(Function):
+    """Per-edge dot products (K.edge_dot); the backward is two edge-weighted SpMMs, one over
+    the pattern and one over its transpose."""
+
+    @staticmethod
+    def forward(ctx, a, b, csr: CSR, heads: int, scale: float):
+        s = K.edge_dot(csr.rowptr, csr.col, a, b, heads=heads, scale=scale)
+        ctx.csr, ctx.heads, ctx.scale = csr, heads, scale
+        ctx.save_for_backward(a, b)
+        return s
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        csr: CSR = ctx.csr
+        w = g.reshape(csr.nnz, ctx.heads)
+        w = (w * ctx.scale if ctx.scale != 1.0 else w).contiguous()
+        da, db = edge_dot_grads(csr, a, b, w, ctx.heads, ctx.needs_input_grad[0],
+                                ctx.needs_input_grad[1])
+        if db is not None and b.shape[0] != csr.num_cols:  # rows no column reaches
+            db = torch.cat([db, db.new_zeros(b.shape[0] - csr.num_cols, b.shape[1])])
+        return da, db, None, None, None
+
+
+def check_edge_dot(a: torch.Tensor, b: torch.Tensor, num_rows: int, num_cols: int,
+                   heads: int) -> None:
+    if a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1] or a.dtype != b.dtype:
+        raise ValueError(f"edge_dot: a and b must be 2-D of one width and dtype, got "
+                         f"{tuple(a.shape)} {a.dtype} and {tuple(b.shape)} {b.dtype}")
+    if heads < 1 or a.shape[1] % heads != 0:
+        raise ValueError(f"edge_dot: heads={heads} must divide the width {a.shape[1]}")
+    if a.shape[0] != num_rows:
+        raise ValueError(f"edge_dot: a has {a.shape[0]} rows, the pattern {num_rows}")
+    if b.shape[0] < num_cols:
+        raise ValueError(f"edge_dot: b has {b.shape[0]} rows, the pattern {num_cols} columns")
+
+
+def edge_dot(a: torch.Tensor, b: torch.Tensor, csr: CSR, heads: int = 1,
+             scale: float = 1.0) -> torch.Tensor:
+    """One score per CSR entry and head (the SDDMM shape):
+    ``s[k, h] = scale * <a[r(k), h-slice], b[col[k], h-slice]>`` for every slot ``k`` of
+    ``csr``, ``r(k)`` the row that holds it; ``[nnz, heads]`` in CSR slot order (fp32 on the
+    GPU, accumulated in fp32 from fp32 or bf16 rows). ``a``: ``[csr.num_rows, F]``, ``b``:
+    ``[>= csr.num_cols, F]``; ``a is b`` scores a square pattern with one embedding
+    (``<z_i, z_j>``) and receives the sum of both gradients. On the GPU one kernel reads each
+    row once per entry and writes nothing per edge but the scores; the backward is two
+    edge-weighted SpMMs. No double backward."""
+    heads = int(heads)
+    check_edge_dot(a, b, csr.num_rows, csr.num_cols, heads)
+    if a is b:
+        a = b = vec_rows(a)
+    else:
+        a, b = vec_rows(a), vec_rows(b)
+    return _EdgeDotFn.apply(a, b, csr, heads, float(scale))
 
 
 class _GatherFn(Function):

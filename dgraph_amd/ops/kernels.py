@@ -91,6 +91,54 @@ def spmm(
     return out
 
 
+def edge_dot(
+    rowptr: torch.Tensor,
+    col: torch.Tensor,
+    a: torch.Tensor,
+    b: torch.Tensor,
+    out: Optional[torch.Tensor] = None,
+    *,
+    heads: int = 1,
+    scale: float = 1.0,
+    row_scale: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Per-edge dot products (SDDMM): ``out[k, h] = scale * row_scale[r(k)] *
+    <a[r(k), h-slice], b[col[k], h-slice]>`` for every CSR slot ``k``, ``r(k)`` the row that
+    holds it; ``[nnz, heads]``. GPU: ``a`` / ``b`` fp32 or bf16 (the same), each with its own
+    row stride (column halves of one buffer are fine), ``out`` contiguous fp32, fp32
+    accumulation in a fixed order (bitwise reproducible, equal for int32 / int64 ``col``); a
+    head width that takes the vector path (:func:`edge_dot_vec_path`) needs bases aligned to
+    4 elements and row strides divisible by 4. CPU: the composed expression, in ``a``'s
+    dtype (fp64 stays fp64, anything else is computed in fp32)."""
+    heads = int(heads)
+    nnz, F = col.numel(), a.shape[1]
+    if heads < 1 or F % heads != 0:
+        raise ValueError(f"edge_dot: heads={heads} must divide the width {F}")
+    if _native_ok(a):
+        if out is None:
+            out = torch.empty(nnz, heads, dtype=torch.float32, device=a.device)
+        if F == 0:
+            return out.zero_()
+        _native.ops().edge_dot(rowptr, col, a, b, out, heads, float(scale), _f32(row_scale))
+        return out
+    return _ref.edge_dot(rowptr, col, a, b, out, heads, scale, row_scale)
+
+
+def edge_dot_vec_path(F: int, heads: int) -> bool:
+    """True when the native :func:`edge_dot` runs ``(F, heads)`` on its 4-elements-per-lane
+    path (``D = F / heads`` a multiple of 4, ``D / 4`` a power of two, ``D <= 1024``), which
+    has the alignment contract; every other shape runs the element-per-lane path."""
+    return bool(_native.ops().edge_dot_vec_path(int(F), int(heads)))
+
+
+def edge_dot_sweep_slots(F: int, heads: int) -> int:
+    """The CSR slots one sweep of the native :func:`edge_dot` launch covers at its grid cap
+    (cap workgroups x 4 waves x the slots a wave takes at a time); a pattern with more has
+    waves that take a second chunk."""
+    ops = _native.ops()
+    return int(ops.edge_dot_grid_cap()) * 4 * int(ops.edge_dot_chunk_slots(int(F), int(heads)))
+
+
 def segment_extreme(
     rowptr: torch.Tensor,
     col: torch.Tensor,

@@ -58,6 +58,28 @@ def spmm(
     return out
 
 
+def edge_dot(rowptr, col, a, b, out=None, heads: int = 1, scale: float = 1.0,
+             row_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``out[k, h] = scale * row_scale[r(k)] * <a[r(k), h-slice], b[col[k], h-slice]>`` per
+    CSR slot as two row gathers and a product (two ``[nnz, F]`` temporaries); fp64 for fp64
+    inputs, else fp32. The edge-weight gradient of :func:`spmm`."""
+    H = max(int(heads), 1)
+    nnz = col.numel()
+    cdt = torch.float64 if a.dtype == torch.float64 else torch.float32
+    rows = _row_ids(rowptr)
+    ar = a.to(cdt)[rows].view(nnz, H, a.shape[1] // H)
+    bc = b.to(cdt)[col.long()].view(nnz, H, a.shape[1] // H)
+    s = (ar * bc).sum(-1)
+    if row_scale is not None:
+        s = s * row_scale[rows].unsqueeze(1)
+    if scale != 1.0:
+        s = s * scale
+    if out is None:
+        return s
+    out.copy_(s.to(out.dtype))
+    return out
+
+
 def spmm_hub_partials(seg_beg, seg_end, col, x, partials, edge_weight=None, col_scale=None):
     """fp32 sums of the hub-tail segments ``col[seg_beg[i]:seg_end[i]]`` (cf. kernels.h;
     fp64 for fp64 inputs, so gradcheck sees the split path at full precision)."""

@@ -670,6 +670,87 @@ class DistGraph:
             K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
         return dx, dt
 
+    def edge_dot(self, a: torch.Tensor, b: torch.Tensor, heads: int = 1, scale: float = 1.0,
+                 halo_rows: Optional[torch.Tensor] = None):
+        """One score per edge at this rank's vertices, local and halo sources
+        (:func:`~dgraph_amd.ops.kernels.edge_dot`): ``scale * <a[i], b[j]>`` per head for
+        every entry ``(i, j)``, with ``b``'s halo rows fetched from their owners. The halo
+        exchange of ``b``'s send rows is posted first, the interior block is scored while
+        they are on the links, then the halo block on the received rows. Returns
+        ``(s_interior, s_halo, saved)``: each block's scores in its own slot order
+        (``self.interior`` / ``self.halo``; ``s_halo`` is ``[0, heads]`` without a halo
+        block), and what :meth:`edge_dot_T` needs. Whole rows are exchanged: a dot product
+        cannot be cut by columns without carrying a partial score from chunk to chunk, so
+        there is no column-chunked exchange here. ``halo_rows`` as in :meth:`aggregate`."""
+        self.edges_aggregated += self.nnz
+        it = self.interior
+        saved = dict(halo=None, heads=int(heads), scale=float(scale))
+        if self.halo is None or halo_rows is not None:
+            s_int = K.edge_dot(it.rowptr, it.col, a, b, heads=heads, scale=scale)
+            if self.halo is None:
+                return s_int, s_int.new_zeros(0, heads), saved
+            saved["halo"] = halo_rows
+            return s_int, K.edge_dot(self.halo.rowptr, self.halo.col, a, halo_rows,
+                                     heads=heads, scale=scale), saved
+        # the exchange depends on the plan alone (a rank with sends and no halo entry posts
+        # it too)
+        recv, work = self.a2a(K.gather_rows(b, self.send_map.idx), async_op=True)
+        if not self.overlap:
+            work.wait()
+        s_int = K.edge_dot(it.rowptr, it.col, a, b, heads=heads, scale=scale)
+        work.wait()
+        saved["halo"] = recv
+        return s_int, K.edge_dot(self.halo.rowptr, self.halo.col, a, recv, heads=heads,
+                                 scale=scale), saved
+
+    def edge_dot_T(self, g_int: torch.Tensor, g_halo: torch.Tensor, a: torch.Tensor,
+                   b: torch.Tensor, saved: dict, halo_out: Optional[torch.Tensor] = None):
+        """Backward of :meth:`edge_dot` (``g_int`` / ``g_halo``: the gradients of the two
+        score blocks; ``a``, ``b`` and ``saved``: the forward's inputs and third result), as
+        edge-weighted SpMMs. ``da``: the interior block over ``b`` and the halo block over the
+        kept halo rows (``beta=1``). ``db``: the halo block's transposed SpMM into ``[H, F]``
+        rows first, which go home by the reverse exchange while the interior's transposed
+        SpMM runs, then the owner-side segment sum of the received rows. ``halo_out``:
+        ``[H, F]`` buffer that keeps the halo gradient here instead (no exchange; the
+        ``halo_rows`` mode of the forward). Returns ``(da, db)``."""
+        from ..ops.aggregate import _slot_transpose, edge_dot_grads
+
+        heads, scale = saved["heads"], saved["scale"]
+        it = self.interior
+        self.edges_aggregated += it.nnz + (self.halo.nnz if self.halo is not None else 0)
+
+        def weights(g, csr):
+            w = g.reshape(csr.nnz, heads)
+            return (w * scale if scale != 1.0 else w).contiguous()
+
+        w_int = weights(g_int, it)
+        if self.halo is None:
+            return edge_dot_grads(it, a, b, w_int, heads)
+        w_halo = weights(g_halo, self.halo)
+        xh = saved["halo"]
+        F = a.shape[1]
+        if self.halo.nnz > 0:
+            ht = _slot_transpose(self.halo)
+            hg = K.spmm(ht.rowptr, ht.col, a, halo_out, edge_weight=w_halo[ht.perm].contiguous(),
+                        heads=heads)
+        else:
+            hg = a.new_zeros(self.H, F) if halo_out is None else halo_out.zero_()
+        work = None
+        if halo_out is None:  # posted whatever this rank's halo block holds
+            sg, work = self.a2a_rev(hg, async_op=True)
+            if not self.overlap:
+                work.wait()
+        da, db = edge_dot_grads(it, a, b, w_int, heads)
+        if self.halo.nnz > 0:
+            hc = self.halo.compact_rows()
+            K.spmm(hc.rowptr, hc.col, xh, da, edge_weight=w_halo, heads=heads, beta=1.0,
+                   row_map=hc.row_map)
+        if work is not None:
+            st = self.send_map.transpose_csr().compact_rows()
+            work.wait()
+            K.spmm(st.rowptr, st.col, sg, db, beta=1.0, split=_hs(st), row_map=st.row_map)
+        return da, db
+
     def _peers(self) -> bool:
         """True when the plan's peers exist (a process group of the plan's size)."""
         import torch.distributed as dist
@@ -955,6 +1036,42 @@ def dist_softmax_aggregate(x: torch.Tensor, graph: DistGraph, t=1.0) -> torch.Te
     :meth:`DistGraph.aggregate_softmax`). ``t`` as there; its gradient is this rank's part
     (``t`` is a replicated parameter: all-reduce it with the other weight gradients)."""
     return _DistSoftmaxAggregateFn.apply(x, as_temperature(t, x), graph)
+
+
+class _DistEdgeDotFn(Function):
+    @staticmethod
+    def forward(ctx, a, b, graph: DistGraph, heads: int, scale: float):
+        s_int, s_halo, saved = graph.edge_dot(a, b, heads, scale)
+        ctx.graph, ctx.heads, ctx.scale, ctx.n_int = graph, heads, scale, s_int.shape[0]
+        ctx.save_for_backward(a, b, saved["halo"])
+        return torch.cat([s_int, s_halo]) if s_halo.shape[0] else s_int
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, halo = ctx.saved_tensors
+        n = ctx.n_int
+        da, db = ctx.graph.edge_dot_T(g[:n], g[n:], a, b,
+                                      dict(halo=halo, heads=ctx.heads, scale=ctx.scale))
+        return da, db, None, None, None
+
+
+def dist_edge_dot(a: torch.Tensor, b: torch.Tensor, graph: DistGraph, heads: int = 1,
+                  scale: float = 1.0) -> torch.Tensor:
+    """Autograd-aware distributed :func:`~dgraph_amd.ops.aggregate.edge_dot`: one score per
+    head for every edge at this rank's vertices, ``scale * <a[i], b[j]>`` with ``b[j]`` local
+    or a halo row (one exchange of whole rows forward, one backward;
+    :meth:`DistGraph.edge_dot`). ``a``, ``b``: ``[L, F]``; ``a is b`` receives the sum of both
+    gradients. Returns ``[graph.nnz, heads]``: the interior block's scores in
+    ``graph.interior``'s slot order, then the halo block's in ``graph.halo``'s."""
+    from ..ops.aggregate import check_edge_dot
+
+    heads = int(heads)
+    check_edge_dot(a, b, graph.L, graph.L, heads)
+    if a is b:
+        a = b = vec_rows(a)
+    else:
+        a, b = vec_rows(a), vec_rows(b)
+    return _DistEdgeDotFn.apply(a, b, graph, heads, float(scale))
 
 
 def dist_aggregate(x: torch.Tensor, graph: DistGraph, mean: bool = True,
