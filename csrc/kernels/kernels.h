@@ -612,4 +612,44 @@ hipError_t sddmm_csr(DType dt, IType it, const int64_t* rowptr, const void* col,
                      int F, int heads, float scale, const float* row_scale, float* s,
                      hipStream_t st);
 
+// DropEdge fused into the CSR aggregation (spmm_drop.hip): sum over a random subgraph drawn
+// per call, with no pattern rebuilt, no mask stored and no atomics. For CSR row r, output
+// row o = row_map ? row_map[r] : r:
+//   out[o, f] = row_scale[o] * sum_{k in row r, keep_k} col_scale[col[k]] * x[col[k], f]
+//               + beta * out[o, f]
+//   keep_k = edge_keep(*seed, dst, src, thr, undirected)                    (philox.h)
+//   rid = row_ids ? row_ids[o] : row_base + o,  cid = col_ids ? col_ids[col[k]] : col_base + col[k]
+//   (dst, src) = transposed ? (cid, rid) : (rid, cid)
+// `transposed` says the CSR is the transposed pattern (rows = sources), which is the whole
+// backward: dx = A_keep^T g with the same seed. No 1 / (1 - p) rescale: the result is the sum
+// over a subgraph. The row of a dropped entry is never loaded (a NaN there cannot reach out).
+// fp32 rows, fp32 accumulation in a fixed order (bitwise reproducible, equal for both index
+// widths); any F >= 1 and row strides ldx / ldo in elements, 16-byte accesses when F, both
+// strides and both bases allow them. row_scale / col_scale / row_map / row_ids / col_ids may
+// be null. seed points to ONE int64 in device memory, read by the kernel, so a captured step
+// draws a new subgraph per replay. nrows < 2^31. Returns before any launch when nrows is 0.
+// Not here: bf16 rows, edge weights, heads, hub splitting, XCD row mapping, column passes.
+struct SpmmDropArgs {
+  const int64_t* rowptr = nullptr;
+  const void* col = nullptr;
+  IType it = IType::I32;
+  int64_t nrows = 0;
+  const int64_t* row_map = nullptr;
+  const int64_t* row_ids = nullptr;
+  const int64_t* col_ids = nullptr;
+  int64_t row_base = 0;
+  int64_t col_base = 0;
+  const int64_t* seed = nullptr;
+  uint32_t thr = 0;
+  bool undirected = false;
+  bool transposed = false;
+};
+hipError_t spmm_drop_f32(const SpmmDropArgs& a, const float* col_scale, const float* row_scale,
+                         const float* x, int64_t ldx, float* out, int64_t ldo, int F, float beta,
+                         hipStream_t st);
+// kept[o] (+= when accumulate) = the number of kept entries of row r: the same mask, counted.
+// Exact; one int32 per row, no feature traffic, no atomics. A row without entries writes 0
+// (adds nothing).
+hipError_t kept_degree(const SpmmDropArgs& a, int32_t* kept, bool accumulate, hipStream_t st);
+
 }  // namespace dgraph

@@ -8,7 +8,8 @@
 //                         key     = (seed & 0xffffffff, seed >> 32))
 //   keep(slot, h) = words[h & 3] >= thr          thr = floor(p 2^32),  0 <= p < 1
 //
-// One call serves four heads. Host and device compile the same text; the only dependency is
+// One call serves four heads. The DropEdge decision (edge_keep, below) is keyed by the two
+// vertex ids of an edge instead of its slot. Host and device compile the same text; the only dependency is
 // <cstdint>. The 32 x 32 -> 64 products become v_mul_lo_u32 / v_mul_hi_u32 on the device.
 #pragma once
 #include <cstdint>
@@ -64,6 +65,31 @@ DG_PHILOX_HD uint32_t attn_keep_bits(uint64_t seed, int64_t slot, uint32_t thr, 
       if (h0 + i < heads && r.w[i] >= thr) bits |= 1u << (h0 + i);
   }
   return bits;
+}
+
+// DropEdge (spmm_drop.hip): the keep decision of the edge dst <- src. It depends on the
+// seed and the two vertex ids alone, never on a CSR slot, so it is the same in the forward
+// pass and over the transposed pattern (no slot map), the same on every partition when the
+// ids are global, and parallel entries with equal (dst, src) share one fate. `undirected`
+// orders the pair first, so both directions of an edge share it too (PyG's
+// force_undirected). Ids are non-negative int64.
+//
+//   (a, b) = undirected ? (min(dst, src), max(dst, src)) : (dst, src)
+//   words  = philox4x32_10(counter = (a & 0xffffffff, a >> 32, b & 0xffffffff, b >> 32),
+//                          key     = (seed & 0xffffffff, seed >> 32))
+//   keep   = words[0] >= thr          thr = floor(p 2^32),  0 <= p < 1  (p = 0 keeps all)
+inline uint32_t edge_keep_threshold(double p) { return attn_keep_threshold(p); }
+
+DG_PHILOX_HD bool edge_keep(uint64_t seed, int64_t dst, int64_t src, uint32_t thr,
+                            bool undirected) {
+  const bool swap = undirected && src < dst;
+  const uint64_t a = static_cast<uint64_t>(swap ? src : dst);
+  const uint64_t b = static_cast<uint64_t>(swap ? dst : src);
+  const Philox4 r = philox4x32_10(static_cast<uint32_t>(a), static_cast<uint32_t>(a >> 32),
+                                  static_cast<uint32_t>(b), static_cast<uint32_t>(b >> 32),
+                                  static_cast<uint32_t>(seed),
+                                  static_cast<uint32_t>(seed >> 32));
+  return r.w[0] >= thr;
 }
 
 }  // namespace dgraph

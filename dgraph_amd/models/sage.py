@@ -31,6 +31,7 @@ from ..ops import kernels as K
 from ..parallel import halo_recompute as _hr
 from ..ops.dense import (col_sum_f32, dual_gemm, dual_gemm_shape_ok, mm_f32,  # noqa: F401
                          tile32_mask_words, wgrad)
+from ..ops.aggregate import EdgeDrop
 from ..parallel.dist_graph import DistGraph, dist_aggregate
 
 
@@ -107,13 +108,36 @@ class SAGELayerFn(Function):
 class SAGEConv(nn.Module):
     """One GraphSAGE layer over a :class:`DistGraph`: the mean aggregator by default;
     ``aggr="max"`` / ``"min"`` take the elementwise extremum over the in-neighbours
-    (GraphSAGE-pool style, not degree-biased), always aggregate-first."""
+    (GraphSAGE-pool style, not degree-biased), always aggregate-first.
+
+    ``drop_edge`` (DropEdge, Rong et al., ICLR 2020): in training every edge is removed with
+    this probability, a fresh subgraph per forward, and the layer computes the mean over the
+    KEPT in-neighbours (:meth:`DistGraph.aggregate_drop`: no pattern is rebuilt, no mask
+    stored); ``drop_undirected`` gives both directions of an edge one fate. The seed of a
+    call is ``base + step * odd constant`` from two int64 device buffers, the step counter
+    advanced in place: no host sync, a new subgraph per replay of a captured step, and the
+    same seed on every rank as long as the ranks call the layer equally often (with
+    ``graph.vertex_ids`` set they then drop exactly the same edges). ``forward(...,
+    drop_seed=)`` fixes it. Evaluation mode and ``drop_edge = 0`` are the plain layer. Mean
+    aggregator only, always aggregate-first; not in the fused executors or the bf16 stack."""
+
+    DROP_SEED_STRIDE = -7046029254386353131  # 0x9E3779B97F4A7C15 as int64 (odd)
 
     def __init__(self, in_dim: int, out_dim: int, bias: bool = True, relu: bool = True,
-                 order: str = "auto", save_agg: Optional[bool] = None, aggr: str = "mean"):
+                 order: str = "auto", save_agg: Optional[bool] = None, aggr: str = "mean",
+                 drop_edge: float = 0.0, drop_undirected: bool = False):
         super().__init__()
         if aggr not in ("mean", "max", "min"):
             raise ValueError(f"unsupported aggr {aggr!r}")
+        if not 0.0 <= float(drop_edge) < 1.0:
+            raise ValueError(f"drop_edge must lie in [0, 1), got {drop_edge}")
+        if drop_edge > 0 and aggr != "mean":
+            raise ValueError(f"drop_edge needs the mean aggregator, got aggr={aggr!r}")
+        self.drop_edge, self.drop_undirected = float(drop_edge), bool(drop_undirected)
+        if self.drop_edge > 0:
+            self.register_buffer("drop_base_seed", torch.tensor([0x5DEECE66D],
+                                                                dtype=torch.int64))
+            self.register_buffer("drop_step", torch.zeros(1, dtype=torch.int64))
         if aggr != "mean" and order == "project_first":
             raise ValueError(f"aggr={aggr!r} is not linear: it cannot run project_first")
         self.aggr = aggr
@@ -138,12 +162,28 @@ class SAGEConv(nn.Module):
             return self.out_dim < self.in_dim
         return self.order == "project_first"
 
-    def forward(self, x: torch.Tensor, graph: DistGraph) -> torch.Tensor:
-        if self.aggr != "mean":
+    def _next_drop_seed(self) -> torch.Tensor:
+        seed = self.drop_base_seed + self.drop_step * self.DROP_SEED_STRIDE
+        self.drop_step.add_(1)
+        return seed
+
+    def forward(self, x: torch.Tensor, graph: DistGraph, drop_seed=None) -> torch.Tensor:
+        dropping = self.drop_edge > 0 and self.training
+        if dropping or self.aggr != "mean":
             # composed from autograd ops: the extremum is not linear, so neither the
-            # project-first order nor SAGELayerFn's single-SpMM backward applies
+            # project-first order nor SAGELayerFn's single-SpMM backward applies, and the
+            # mean over a random subgraph leaves SAGELayerFn untouched
             dt = x.dtype
-            a = dist_aggregate(x, graph, reduce=self.aggr)
+            if dropping:
+                if drop_seed is None:
+                    drop_seed = self._next_drop_seed()
+                elif not isinstance(drop_seed, torch.Tensor):
+                    drop_seed = torch.tensor([int(drop_seed)], dtype=torch.int64,
+                                             device=x.device)
+                a = dist_aggregate(x, graph, mean=True, drop=EdgeDrop(
+                    self.drop_edge, drop_seed, self.drop_undirected))
+            else:
+                a = dist_aggregate(x, graph, reduce=self.aggr)
             y = x @ self.w_self.to(dt) + a @ self.w_neigh.to(dt)
             if self.bias is not None:
                 y = y + self.bias.to(dt)

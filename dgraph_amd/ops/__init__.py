@@ -10,6 +10,9 @@ def __getattr__(name):
     if name == "edge_dot":  # next to aggregate (ops/aggregate.py)
         from .aggregate import edge_dot
         return edge_dot
+    if name == "EdgeDrop":  # the DropEdge spec of aggregate(..., drop=)
+        from .aggregate import EdgeDrop
+        return EdgeDrop
     if name == "gatv2_attention":
         from .gatv2 import gatv2_attention
         return gatv2_attention

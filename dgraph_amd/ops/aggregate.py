@@ -2,6 +2,8 @@
 
 * :func:`aggregate` — CSR SpMM (sum / mean / edge-weighted, multi-head); backward is the
   same kernel on the cached transposed CSR (or on the same CSR for symmetric patterns).
+  With an :class:`EdgeDrop` the sum / mean runs over a random subgraph drawn per call
+  (DropEdge), fused into the aggregation kernel.
 * :func:`aggregate_multi` — mean, max, min and standard deviation of the same neighbour
   rows in ONE gather pass (the PNA aggregators), as column blocks of one ``[R, A*F]`` tensor.
 * :func:`softmax_aggregate` — the learnable softmax aggregation (per channel, the score is
@@ -16,6 +18,7 @@
 """
 from __future__ import annotations
 
+from dataclasses import dataclass
 from typing import Optional
 
 import torch
@@ -226,14 +229,102 @@ def softmax_aggregate(x: torch.Tensor, csr: CSR, t=1.0) -> torch.Tensor:
     return _SoftmaxAggregateFn.apply(vec_rows(x), as_temperature(t, x), csr)
 
 
+@dataclass
+class EdgeDrop:
+    """DropEdge (Rong et al., ICLR 2020; PyG's ``dropout_edge``) for one aggregation call:
+    every edge is removed with probability ``p``, a fresh subgraph per ``seed``. The pattern
+    is never rebuilt and no mask is stored: the keep decision of an edge is a pure function
+    of ``(seed, destination id, source id)`` (:func:`~dgraph_amd.ops.philox.edge_keep_mask`),
+    regenerated by the forward and by the transposed pass.
+
+    ``seed``: a 1-element int64 tensor that the kernels read from device memory (so a
+    captured step draws a new subgraph per replay; a Python int is wrapped); it must hold its
+    value until the backward has run. ``undirected``: both directions of an edge share one
+    fate (PyG's ``force_undirected``), so an undirected graph stays undirected. Parallel
+    entries with equal ``(dst, src)`` always share one fate. The result is the aggregation
+    over the subgraph: no ``1 / (1 - p)`` rescale."""
+
+    p: float
+    seed: torch.Tensor
+    undirected: bool = False
+
+    def __post_init__(self):
+        self.p = float(self.p)
+        if not 0.0 <= self.p < 1.0:
+            raise ValueError(f"EdgeDrop: p must lie in [0, 1), got {self.p}")
+        if not isinstance(self.seed, torch.Tensor):
+            self.seed = torch.tensor([int(self.seed)], dtype=torch.int64)
+        if self.seed.numel() != 1 or self.seed.dtype != torch.int64:
+            raise ValueError("EdgeDrop: seed must be a 1-element int64 tensor")
+
+
+def inv_kept(kept: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """``1 / max(kept, 1)``: the row scale of the mean over the kept entries."""
+    return 1.0 / kept.clamp(min=1).to(torch.float64 if dtype == torch.float64 else torch.float32)
+
+
+class _AggregateDropFn(Function):
+    """Sum / mean over the kept entries of each row (K.spmm_drop). The forward saves only the
+    kept degrees (for mean); the backward is the same kernel over the transposed pattern with
+    ``transposed=True``, which regenerates the same decisions from the vertex ids."""
+
+    @staticmethod
+    def forward(ctx, x, csr: CSR, drop: EdgeDrop, mean: bool, row_ids, col_ids):
+        ids = dict(seed=drop.seed, p=drop.p, undirected=drop.undirected)
+        scale = None
+        if mean:
+            kept = K.kept_degree(csr.rowptr, csr.col, row_ids=row_ids, col_ids=col_ids,
+                                 num_cols=x.shape[0], **ids)
+            scale = inv_kept(kept, x.dtype)
+        out = K.spmm_drop(csr.rowptr, csr.col, x, row_scale=scale, row_ids=row_ids,
+                          col_ids=col_ids, **ids)
+        ctx.csr, ctx.drop, ctx.mean, ctx.ids, ctx.x_rows = csr, drop, mean, (row_ids, col_ids), \
+            x.shape[0]
+        ctx.save_for_backward(kept if mean else None)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (kept,) = ctx.saved_tensors
+        drop: EdgeDrop = ctx.drop
+        row_ids, col_ids = ctx.ids
+        # a symmetric pattern is its own transpose (CSR.transpose returns it): read as
+        # "rows are sources" it lists each source's destinations, whichever way the key is
+        # formed, so transposed=True is all either case needs
+        t = ctx.csr.transpose()
+        g = vec_rows(g)
+        gx = K.spmm_drop(t.rowptr, t.col, g, seed=drop.seed, p=drop.p,
+                         undirected=drop.undirected, transposed=True,
+                         col_scale=inv_kept(kept, g.dtype) if ctx.mean else None,
+                         row_ids=col_ids, col_ids=row_ids)
+        if ctx.x_rows != t.num_rows:  # rows no column reaches
+            gx = torch.cat([gx, gx.new_zeros(ctx.x_rows - t.num_rows, gx.shape[1])])
+        return gx, None, None, None, None, None
+
+
 def aggregate(
     x: torch.Tensor,
     csr: CSR,
     edge_weight: Optional[torch.Tensor] = None,
     reduce: str = "sum",
     heads: int = 1,
+    drop: Optional[EdgeDrop] = None,
+    row_ids: Optional[torch.Tensor] = None,
+    col_ids: Optional[torch.Tensor] = None,
 ) -> torch.Tensor:
     """``out[r] = reduce_{j in N(r)} w_j * x[j]`` over the CSR rows.
+
+    ``drop``: an :class:`EdgeDrop`; the ``"sum"`` / ``"mean"`` then runs over a random
+    subgraph drawn from its seed (``"mean"`` divides by the number of KEPT entries,
+    ``max(kept, 1)``; a row that lost every entry gives 0), on the GPU in one fused fp32 kernel
+    that never loads the row of a dropped entry. ``row_ids`` / ``col_ids`` (int64, one per CSR
+    row / per row of ``x``) are the vertex ids the decision is keyed by; by default the row
+    and column numbers. A ``symmetric`` CSR runs its backward on itself. ``drop=None`` or
+    ``p == 0`` is the plain call, the same kernels and the same bits. Not supported under
+    ``drop`` (``ValueError``): edge weights, ``heads > 1``, any other ``reduce``; bf16 rows,
+    hub splitting, the fused executors and the attention layers do not take it either. A GCN
+    renormalised by kept degrees would combine :func:`~dgraph_amd.ops.kernels.kept_degree`
+    with ``row_scale`` / ``col_scale`` of :func:`~dgraph_amd.ops.kernels.spmm_drop`.
 
     ``edge_weight`` is ``[nnz]`` or ``[nnz, heads]`` in CSR slot order; with heads > 1
     the feature dim is split into ``heads`` equal slices, each scaled by its head weight.
@@ -249,6 +340,15 @@ def aggregate(
     ``reduce="softmax"``: :func:`softmax_aggregate` at temperature 1, unweighted and
     single-head.
     """
+    if drop is not None and drop.p > 0.0:
+        if reduce not in ("sum", "mean"):
+            raise ValueError(f"drop supports reduce 'sum' / 'mean', got {reduce!r}")
+        if edge_weight is not None:
+            raise ValueError("drop takes no edge weights")
+        if heads != 1:
+            raise ValueError(f"drop takes one head, got heads={heads}")
+        return _AggregateDropFn.apply(vec_rows(x), csr, drop, reduce == "mean", row_ids,
+                                      col_ids)
     if reduce == "softmax":
         if edge_weight is not None:
             raise ValueError("reduce='softmax' takes no edge weights")

@@ -15,6 +15,7 @@ from typing import Optional
 import torch
 
 from .. import _native
+from . import philox as _philox
 from . import reference as _ref
 
 
@@ -88,6 +89,140 @@ def spmm(
         _ref.spmm_hub_partials(split.seg_beg, split.seg_end, col, x, part, edge_weight,
                                col_scale)
         _ref.spmm_hub_reduce(part, split.hub_seg_ptr, split.hub_rows, out, row_scale)
+    return out
+
+
+def _seed_tensor(seed, device) -> torch.Tensor:
+    """The DropEdge seed as ONE int64 on ``device`` (the kernels read it from memory)."""
+    if isinstance(seed, torch.Tensor):
+        if seed.numel() != 1 or seed.dtype != torch.int64:
+            raise ValueError("seed must be a Python int or a 1-element int64 tensor")
+        return seed if seed.device == device else seed.to(device)
+    return torch.tensor([int(seed)], dtype=torch.int64, device=device)
+
+
+def _drop_entries(rowptr, col, seed, p, undirected, transposed, row_map, row_ids, col_ids,
+                  row_base, col_base):
+    """``(out_rows [R], entry_rows [nnz], keep [nnz])`` of the DropEdge contract in torch:
+    the output row of every CSR row and entry, and the keep decision of every entry."""
+    R = rowptr.numel() - 1
+    out_rows = row_map.long() if row_map is not None else torch.arange(R, device=col.device)
+    rows = torch.repeat_interleave(out_rows, (rowptr[1:] - rowptr[:-1]).long())
+    c = col.long()
+    rid = row_ids[rows] if row_ids is not None else rows + int(row_base)
+    cid = col_ids[c] if col_ids is not None else c + int(col_base)
+    dst, src = (cid, rid) if transposed else (rid, cid)
+    return out_rows, rows, _philox.edge_keep_mask(seed, dst, src, p, undirected)
+
+
+def spmm_drop(
+    rowptr: torch.Tensor,
+    col: torch.Tensor,
+    x: torch.Tensor,
+    out: Optional[torch.Tensor] = None,
+    *,
+    seed,
+    p: float,
+    undirected: bool = False,
+    transposed: bool = False,
+    col_scale: Optional[torch.Tensor] = None,
+    row_scale: Optional[torch.Tensor] = None,
+    beta: float = 0.0,
+    row_map: Optional[torch.Tensor] = None,
+    row_ids: Optional[torch.Tensor] = None,
+    col_ids: Optional[torch.Tensor] = None,
+    row_base: int = 0,
+    col_base: int = 0,
+) -> torch.Tensor:
+    """CSR aggregation over a random subgraph (DropEdge) drawn from ``seed``; no pattern is
+    rebuilt and no mask stored. For CSR row ``r``, output row ``o = row_map[r]`` (or ``r``)::
+
+        out[o] = row_scale[o] * sum_{k in row r, keep_k} col_scale[c_k] * x[c_k] + beta * out[o]
+        keep_k = edge_keep_mask(seed, dst, src, p, undirected)        (ops/philox.py)
+        rid = row_ids[o] (or row_base + o),  cid = col_ids[c_k] (or col_base + c_k)
+        (dst, src) = (cid, rid) if transposed else (rid, cid)
+
+    ``transposed`` says the CSR is the transposed pattern (rows are sources), which is the
+    whole backward: ``dx = A_keep^T g`` with the same seed. The sum is over a subgraph: no
+    ``1 / (1 - p)`` rescale. Parallel entries with equal ``(dst, src)`` share one fate.
+    ``seed``: a Python int or a 1-element int64 tensor on ``x``'s device, which the kernel
+    reads (a captured step draws a new subgraph per replay). ``row_map`` needs ``out``.
+
+    GPU: fp32 rows with any row strides, fp32 accumulation in a fixed order (bitwise
+    reproducible, equal for int32 / int64 ``col``); the row of a dropped entry is never
+    loaded. Not supported: bf16 rows, edge weights, heads, hub splitting. CPU: the contract
+    in torch (``index_add_`` over the kept entries) in ``x``'s dtype."""
+    R, F = rowptr.numel() - 1, x.shape[1]
+    if row_map is not None and out is None:
+        raise ValueError("spmm_drop: row_map needs an explicit out")
+    if out is None:
+        out = torch.empty(R, F, dtype=x.dtype, device=x.device)
+        beta = 0.0
+    seed = _seed_tensor(seed, x.device)
+    if _native_ok(x):
+        _native.ops().spmm_drop_f32(rowptr, col, x, out, seed, float(p), bool(undirected),
+                                    bool(transposed), _f32(col_scale), _f32(row_scale),
+                                    float(beta), row_map, row_ids, col_ids, int(row_base),
+                                    int(col_base))
+        return out
+    out_rows, rows, keep = _drop_entries(rowptr, col, seed, p, undirected, transposed, row_map,
+                                         row_ids, col_ids, row_base, col_base)
+    ck = col.long()[keep]
+    contrib = x[ck]
+    if col_scale is not None:
+        contrib = contrib * col_scale[ck].to(x.dtype)[:, None]
+    agg = torch.zeros(out.shape[0], F, dtype=x.dtype, device=x.device)
+    agg.index_add_(0, rows[keep], contrib)
+    agg = agg[out_rows]
+    if row_scale is not None:
+        agg = agg * row_scale[out_rows].to(x.dtype)[:, None]
+    if beta != 0.0:
+        agg = agg + beta * out[out_rows].to(x.dtype)
+    out[out_rows] = agg.to(out.dtype)
+    return out
+
+
+def kept_degree(
+    rowptr: torch.Tensor,
+    col: torch.Tensor,
+    out: Optional[torch.Tensor] = None,
+    *,
+    seed,
+    p: float,
+    undirected: bool = False,
+    transposed: bool = False,
+    accumulate: bool = False,
+    row_map: Optional[torch.Tensor] = None,
+    row_ids: Optional[torch.Tensor] = None,
+    col_ids: Optional[torch.Tensor] = None,
+    num_cols: Optional[int] = None,
+    row_base: int = 0,
+    col_base: int = 0,
+) -> torch.Tensor:
+    """``kept[o]`` (int32) = the number of entries of CSR row ``r`` that :func:`spmm_drop`
+    keeps with the same arguments (``+=`` with ``accumulate``: the second block of a
+    two-source graph). An exact integer result; no feature traffic, no atomics. ``num_cols``:
+    the number of source rows (what ``col_ids`` must cover); by default ``col_ids``'s length.
+    ``row_map`` / ``accumulate`` need ``out``."""
+    R = rowptr.numel() - 1
+    if (row_map is not None or accumulate) and out is None:
+        raise ValueError("kept_degree: row_map / accumulate need an explicit out")
+    if out is None:
+        out = torch.empty(R, dtype=torch.int32, device=col.device)
+    seed = _seed_tensor(seed, col.device)
+    if _native_ok(col):
+        if num_cols is None:
+            num_cols = col_ids.numel() if col_ids is not None else 0
+        _native.ops().kept_degree(rowptr, col, out, seed, float(p), bool(undirected),
+                                  bool(transposed), bool(accumulate), row_map, row_ids, col_ids,
+                                  int(num_cols), int(row_base), int(col_base))
+        return out
+    out_rows, rows, keep = _drop_entries(rowptr, col, seed, p, undirected, transposed, row_map,
+                                         row_ids, col_ids, row_base, col_base)
+    cnt = torch.zeros(out.shape[0], dtype=torch.int64, device=col.device)
+    cnt.index_add_(0, rows[keep], torch.ones_like(rows[keep]))
+    cnt = cnt[out_rows].to(torch.int32)
+    out[out_rows] = out[out_rows] + cnt if accumulate else cnt
     return out
 
 

@@ -1,4 +1,5 @@
-"""Philox4x32-10 and the attention-dropout keep mask in torch integer ops.
+"""Philox4x32-10, the attention-dropout keep mask and the DropEdge keep decision
+(:func:`edge_keep_mask`) in torch integer ops.
 
 The same generator as ``csrc/kernels/philox.h`` (Salmon et al., SC'11; the Random123 /
 cuRAND / torch generator), bit for bit: the fused dropout kernels
@@ -77,3 +78,32 @@ def attn_keep_mask(seed: Union[int, torch.Tensor], num_slots: int, heads: int, p
         torch.zeros((), dtype=torch.int64, device=device)), -1)      # [S, groups, 4]
     words = philox4x32_10(counter, key)                               # [S, groups, 4]
     return (words.reshape(num_slots, 4 * groups)[:, :heads] >= thr)
+
+
+def edge_keep_mask(seed: Union[int, torch.Tensor], dst_ids: torch.Tensor, src_ids: torch.Tensor,
+                   p: float, undirected: bool = False) -> torch.Tensor:
+    """The DropEdge keep decision of the edges ``dst_ids[i] <- src_ids[i]`` (bool, their
+    broadcast shape), bit for bit ``edge_keep`` of ``csrc/kernels/philox.h``::
+
+        (a, b) = (dst, src)                          directed
+        (a, b) = (min(dst, src), max(dst, src))      undirected
+        words  = philox4x32_10(counter = (a & M32, a >> 32, b & M32, b >> 32),
+                               key     = (seed & M32, seed >> 32))
+        keep   = words[0] >= floor(p * 2^32)         0 <= p < 1;  p = 0 keeps everything
+
+    It depends on the seed and the two non-negative int64 vertex ids alone, not on a CSR
+    slot: the transposed pass regenerates it without a slot map, global ids make it the same
+    on every partition, ``undirected`` gives both directions of an edge one fate, and
+    parallel entries with equal ``(dst, src)`` always share one. ``seed``: a Python int or a
+    1-element int64 tensor (no host sync)."""
+    thr = keep_threshold(p)
+    dst, src = torch.broadcast_tensors(dst_ids.long(), src_ids.long())
+    device = dst.device
+    if isinstance(seed, torch.Tensor):
+        sd = seed.reshape(()).long().to(device)
+    else:
+        sd = torch.tensor(int(seed), dtype=torch.int64, device=device)
+    key = torch.stack([sd & M32, (sd >> 32) & M32])
+    a, b = (torch.minimum(dst, src), torch.maximum(dst, src)) if undirected else (dst, src)
+    counter = torch.stack([a & M32, (a >> 32) & M32, b & M32, (b >> 32) & M32], -1)
+    return philox4x32_10(counter, key)[..., 0] >= thr

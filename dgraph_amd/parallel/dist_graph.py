@@ -25,7 +25,8 @@ from torch.autograd import Function
 
 from ..comm.alltoallv import AllToAllV
 from ..ops import kernels as K
-from ..ops.aggregate import as_temperature, check_aggregators, multi_blocks, vec_rows
+from ..ops.aggregate import (EdgeDrop, as_temperature, check_aggregators, inv_kept,
+                             multi_blocks, vec_rows)
 from ..ops.csr import CSR, IndexMap
 
 
@@ -123,6 +124,12 @@ class DistGraph:
         # edges (nonzeros) aggregated by every call so far, forward and transposed:
         # bench.py reports the per-step delta as ``edges_aggregated_per_step``
         self.edges_aggregated = 0
+        # optional int64 [L + H]: the global ids of the local rows, then of the halo rows
+        # (build_partition returns ``offsets`` and ``halo_gids``), which the DropEdge
+        # decision of aggregate_drop is keyed by; W = 1, 2, 3 then drop exactly the same
+        # edges. None: the local numbering 0 .. L + H, which is still consistent between the
+        # forward and the backward of a rank, but not across partitions.
+        self.vertex_ids: Optional[torch.Tensor] = None
         if self.H > 0 or (send_local_idx is not None and send_local_idx.numel() > 0):
             self.interior, self.halo = csr.split_columns(self.L)
             self.interior.symmetric = symmetric
@@ -455,6 +462,91 @@ class DistGraph:
             work.wait()
             oc = out if (c0, c1) == (0, F) else out[:, c0:c1]
             K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
+        return out
+
+    def _drop_ids(self):
+        """``(ids of the local rows [L], ids of the halo rows [H])`` the DropEdge decision is
+        keyed by, or ``(None, None)`` for the local numbering (halo row j is L + j)."""
+        v = self.vertex_ids
+        if v is None:
+            return None, None
+        if v.dtype != torch.int64 or v.dim() != 1 or v.numel() != self.L + self.H:
+            raise ValueError(f"vertex_ids must be int64 [{self.L + self.H}] (local rows, then "
+                             f"halo rows), got {v.dtype} {tuple(v.shape)}")
+        if v.device != self.device:
+            v = self.vertex_ids = v.to(self.device)
+        return v[:self.L], v[self.L:]
+
+    def aggregate_drop(self, x: torch.Tensor, drop, mean: bool = True,
+                       out: Optional[torch.Tensor] = None):
+        """Sum / mean over the in-neighbours that ``drop`` (an
+        :class:`~dgraph_amd.ops.aggregate.EdgeDrop`) keeps, local and halo, on the schedule
+        of :meth:`aggregate`: the exchange is posted, the kept degrees are counted over the
+        interior block and then over the compacted halo block, the interior pass runs while
+        the halo rows are on the links, and the halo pass adds to it (``beta = 1``), both with
+        ``row_scale = 1 / max(kept, 1)`` for mean. Returns ``(out, kept)``; ``kept`` (int32
+        ``[L]``, ``None`` for sum) is what :meth:`aggregate_drop_T` needs. The decision is
+        keyed by :attr:`vertex_ids`. Whole rows in one exchange: no column chunks, no
+        ``static=`` / ``halo_rows=``; fp32 rows on the GPU."""
+        self.edges_aggregated += self.nnz  # entries visited, kept or not
+        kw = dict(seed=drop.seed, p=drop.p, undirected=drop.undirected)
+        loc, hal = self._drop_ids()
+        it, hc = self.interior, None
+        x = vec_rows(x)
+        if out is None:
+            out = torch.empty(self.L, x.shape[1], dtype=x.dtype, device=x.device)
+        if self.halo is not None:
+            # the exchange depends on the plan alone (a rank with sends and no halo row
+            # posts it too)
+            recv, work = self.a2a(K.gather_rows(x, self.send_map.idx), async_op=True)
+            if not self.overlap:
+                work.wait()
+            hc = self.halo.compact_rows()
+        kept = rs = None
+        if mean:
+            kept = K.kept_degree(it.rowptr, it.col, row_ids=loc, col_ids=loc, num_cols=self.L,
+                                 **kw)
+            if hc is not None:
+                K.kept_degree(hc.rowptr, hc.col, kept, accumulate=True, row_map=hc.row_map,
+                              row_ids=loc, col_ids=hal, num_cols=self.H, col_base=self.L, **kw)
+            rs = inv_kept(kept, x.dtype)
+        K.spmm_drop(it.rowptr, it.col, x, out, row_scale=rs, row_ids=loc, col_ids=loc, **kw)
+        if hc is not None:
+            work.wait()
+            K.spmm_drop(hc.rowptr, hc.col, recv, out, row_scale=rs, beta=1.0,
+                        row_map=hc.row_map, row_ids=loc, col_ids=hal, col_base=self.L, **kw)
+        return out, kept
+
+    def aggregate_drop_T(self, g: torch.Tensor, drop, mean: bool = True,
+                         kept: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Transposed :meth:`aggregate_drop` (its backward, with the same ``drop``) on the
+        schedule of :meth:`aggregate_T`: halo-transposed pass, reverse exchange,
+        interior-transposed pass, owner-side segment sum. The passes run over the transposed
+        blocks with ``transposed=True``, which regenerates the forward's decisions from the
+        vertex ids; a ``symmetric`` interior runs on itself. ``kept``: the forward's kept
+        degrees (mean)."""
+        if mean and kept is None:
+            raise ValueError("aggregate_drop_T: mean needs the forward's kept degrees")
+        kw = dict(seed=drop.seed, p=drop.p, undirected=drop.undirected, transposed=True)
+        loc, hal = self._drop_ids()
+        g = vec_rows(g)
+        cs = inv_kept(kept, g.dtype) if mean else None
+        it = self.interior.transpose()  # the interior itself when symmetric
+        self.edges_aggregated += it.nnz + (self.halo.nnz if self.halo is not None else 0)
+        if self.halo is not None:
+            ht = self.halo.transpose()
+            hg = K.spmm_drop(ht.rowptr, ht.col, g, col_scale=cs, row_ids=hal, col_ids=loc,
+                             row_base=self.L, **kw)
+            sg, work = self.a2a_rev(hg, async_op=True)
+            if not self.overlap:
+                work.wait()
+        out = K.spmm_drop(it.rowptr, it.col, g, out, col_scale=cs, row_ids=loc, col_ids=loc,
+                          **kw)
+        if self.halo is not None:
+            work.wait()
+            st = self.send_map.transpose_csr().compact_rows()
+            K.spmm(st.rowptr, st.col, sg, out, beta=1.0, split=_hs(st), row_map=st.row_map)
         return out
 
     def degree(self) -> torch.Tensor:
@@ -963,6 +1055,20 @@ class _DistAggregateFn(Function):
         return ctx.graph.aggregate_T(g, ctx.mean), None, None
 
 
+class _DistAggregateDropFn(Function):
+    @staticmethod
+    def forward(ctx, x, graph: DistGraph, mean: bool, drop: EdgeDrop):
+        out, kept = graph.aggregate_drop(x, drop, mean)
+        ctx.graph, ctx.mean, ctx.drop = graph, mean, drop
+        ctx.save_for_backward(kept)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (kept,) = ctx.saved_tensors
+        return ctx.graph.aggregate_drop_T(g, ctx.drop, ctx.mean, kept), None, None, None
+
+
 class _DistAggregateExtremeFn(Function):
     @staticmethod
     def forward(ctx, x, graph: DistGraph, minimum: bool):
@@ -1075,11 +1181,19 @@ def dist_edge_dot(a: torch.Tensor, b: torch.Tensor, graph: DistGraph, heads: int
 
 
 def dist_aggregate(x: torch.Tensor, graph: DistGraph, mean: bool = True,
-                   reduce: Optional[str] = None) -> torch.Tensor:
+                   reduce: Optional[str] = None,
+                   drop: Optional[EdgeDrop] = None) -> torch.Tensor:
     """Autograd-aware distributed neighbourhood aggregation: sum or mean (``mean``), or
     with ``reduce="max"`` / ``"min"`` the elementwise extremum over the in-neighbours (its
     gradient goes to the one winning entry, :meth:`DistGraph.aggregate_extreme`), or with
-    ``reduce="softmax"`` :func:`dist_softmax_aggregate` at temperature 1."""
+    ``reduce="softmax"`` :func:`dist_softmax_aggregate` at temperature 1. ``drop``: the sum
+    / mean runs over the random subgraph an :class:`~dgraph_amd.ops.aggregate.EdgeDrop`
+    keeps (:meth:`DistGraph.aggregate_drop`; mean over the kept in-neighbours); ``None`` or
+    ``p == 0`` is the plain call."""
+    if drop is not None and drop.p > 0.0:
+        if reduce is not None:
+            raise ValueError(f"drop supports sum / mean only, got reduce={reduce!r}")
+        return _DistAggregateDropFn.apply(x, graph, mean, drop)
     if reduce is None:
         return _DistAggregateFn.apply(x, graph, mean)
     if reduce == "softmax":
