@@ -213,6 +213,37 @@ hipError_t segment_softmax_bwd(IType it, const int64_t* t_rowptr, const void* t_
                                float* dt_part, int64_t nrows, int F, hipStream_t stream);
 
 // ---------------------------------------------------------------------------
+// Softmax aggregation with edge features (spmm_softmax_edge.hip), fp32: GENConv's message
+// with edge_dim, formed per CSR slot k of row r inside the gather:
+//   z = x[col[k], f] + e[k, f],  m = (relu ? max(z, 0) : z) + eps
+//   lse[r, f] = log sum_k exp(t[f] m_k),  out[r, f] = sum_k exp(t[f] m_k - lse[r, f]) m_k
+// e is [nnz, F], one row per slot in slot order, with its own row stride; everything else as
+// segment_softmax_fwd (empty row: 0 / -inf; second; row_map).
+// Backward, destination side, over the SAME pattern of any block of the entries, given the
+// FINAL (out, lse); g / out_fwd / lse are indexed by the CSR row:
+//   w = exp(t[f] m - lse[r, f]),  d = m - out_fwd[r, f]
+//   de[k, f] = w g[r, f] (1 + t[f] d) where !relu or z > 0 (strict), else exactly 0
+//   dt[f]    = sum_k w g[r, f] d^2 = the column sums of dt_part
+// Every slot's de row is written, F columns each. dt_part is
+// [segment_softmax_edge_dt_parts(nrows), F] contiguous, every row written; null skips it.
+// The source side is no kernel: dx[c] = sum_{k: col[k] = c} de[k], a row-sum SpMM of de over
+// the slot-transposed pattern. No atomics; bitwise reproducible.
+// ---------------------------------------------------------------------------
+int64_t segment_softmax_edge_dt_parts(int64_t nrows);
+hipError_t segment_softmax_edge_fwd(IType it, const int64_t* rowptr, const void* col,
+                                    const float* x, int64_t ldx, const float* e, int64_t lde,
+                                    const float* t, float* out, int64_t ldo, float* lse,
+                                    int64_t ldl, int64_t nrows, int F, bool relu, float eps,
+                                    bool second, const int64_t* row_map, hipStream_t stream);
+hipError_t segment_softmax_edge_bwd(IType it, const int64_t* rowptr, const void* col,
+                                    const float* x, int64_t ldx, const float* e, int64_t lde,
+                                    const float* t, const float* g, int64_t ldg,
+                                    const float* out_fwd, int64_t ldof, const float* lse,
+                                    int64_t ldl, float* de, int64_t ldde, float* dt_part,
+                                    int64_t nrows, int F, bool relu, float eps,
+                                    hipStream_t stream);
+
+// ---------------------------------------------------------------------------
 // Row copy with optional source and destination index (K4/K7/K8 replacement, K-new-1).
 //   out[dst(i)] (+)= x[src(i)]   for i in [0, n)
 // src/dst null == identity. src(i) < 0 writes zeros; dst(i) < 0 skips the row.

@@ -1,5 +1,5 @@
 """GENeralized graph convolution with softmax aggregation (DeeperGCN; PyG's ``GENConv`` with
-``aggr="softmax"`` and no edge features) on a vertex-partitioned graph.
+``aggr="softmax"``, with or without edge features) on a vertex-partitioned graph.
 
 ``CommAwareGENConv`` computes, for every local vertex ``i``::
 
@@ -12,6 +12,15 @@ with ``x_j -> lin_src x_j`` and ``x_i -> lin_dst x_i`` when ``in_channels != out
 (``channelwise_t``: ``[out_channels]``). ``t = 0`` is the mean aggregator, a large ``|t|``
 approaches max / min.
 
+With ``edge_dim`` the message depends on the edge, as PyG's ``GENConv(edge_dim=)``::
+
+    msg_ij = relu(x_j + e_ij) + eps              # per edge i <- j
+
+with ``e_ij -> lin_edge e_ij`` when ``edge_dim != out_channels``. ``forward`` then takes
+``edge_attr``, the pair ``(interior block, halo block)`` of ``[nnz_block, edge_dim]`` rows in
+the slot order of ``graph.interior`` / ``graph.halo`` (per-slot rows of the unsplit pattern are
+cut into the pair by :meth:`~dgraph_amd.ops.csr.CSR.split_edge_values`).
+
 MI355X formulation:
 
 * the message depends on the source vertex alone, so it is formed once per vertex (plain
@@ -21,25 +30,32 @@ MI355X formulation:
   element, nothing written per edge, one halo exchange hidden under the interior pass); the
   backward recomputes every weight from ``(out, lse)`` and gives ``dx`` and ``dt`` from one
   kernel per block;
+* with ``edge_dim`` the message cannot be formed per vertex: the exchange carries
+  ``lin_src x`` and ``x_j + e_ij``, ``relu`` and ``+ eps`` run per slot inside the gather
+  (:func:`~dgraph_amd.parallel.dist_graph.dist_softmax_aggregate_edge`), so nothing ``[E,
+  C]`` is written forward beyond the projected edge rows; the backward writes the edge
+  gradient once (``lin_edge``'s weight gradient reads it) and sums it once for ``dx``;
 * ``t`` is a replicated parameter: its gradient is this rank's part and is all-reduced with
   the other weight gradients.
 
-Out of scope here: ``powermean`` and the other GENConv aggregators, edge features, message
-norm, bf16, fusing ``relu + eps`` into the gather, and the wiring into ``GraphSAGE``, the
-fused executor or ``bench.py``.
+Out of scope here: ``powermean`` and the other GENConv aggregators, message norm, bf16 (edge
+rows included), fusing ``relu + eps`` into the gather of the layer WITHOUT edge features, and
+the wiring into ``GraphSAGE``, the fused executor or ``bench.py``.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
-from ..parallel.dist_graph import DistGraph, dist_softmax_aggregate
+from ..parallel.dist_graph import (DistGraph, dist_softmax_aggregate,
+                                   dist_softmax_aggregate_edge)
 
 
 class CommAwareGENConv(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, t: float = 1.0,
                  learn_t: bool = False, channelwise_t: bool = False, eps: float = 1e-7,
-                 expansion: int = 2, norm: bool = True, bias: bool = False, comm=None):
+                 expansion: int = 2, norm: bool = True, bias: bool = False, comm=None,
+                 edge_dim=None):
         super().__init__()
         self.in_channels, self.out_channels = in_channels, out_channels
         self.eps = eps
@@ -56,6 +72,9 @@ class CommAwareGENConv(nn.Module):
         else:
             self.register_module("lin_src", None)
             self.register_module("lin_dst", None)
+        self.edge_dim = edge_dim
+        if edge_dim is not None and edge_dim != out_channels:
+            self.lin_edge = nn.Linear(edge_dim, out_channels, bias=bias)
         hidden = expansion * out_channels
         layers = [nn.Linear(out_channels, hidden, bias=bias)]
         if norm:
@@ -70,9 +89,31 @@ class CommAwareGENConv(nn.Module):
         if isinstance(self.t, nn.Parameter):
             nn.init.constant_(self.t, self.init_t)
 
-    def forward(self, x: torch.Tensor, graph: DistGraph) -> torch.Tensor:
+    def _edge_rows(self, edge_attr):
+        """The ``(interior, halo)`` edge blocks at ``out_channels`` width."""
+        if not isinstance(edge_attr, (tuple, list)) or len(edge_attr) != 2:
+            raise ValueError("edge_attr must be the pair (interior block, halo block)")
+        rows = []
+        for e in edge_attr:
+            if e is not None:
+                if e.dim() != 2 or e.shape[1] != self.edge_dim:
+                    raise ValueError(f"edge_attr blocks must be [nnz_block, {self.edge_dim}], "
+                                     f"got {tuple(e.shape)}")
+                if self.edge_dim != self.out_channels:
+                    e = self.lin_edge(e)
+            rows.append(e)
+        return rows
+
+    def forward(self, x: torch.Tensor, graph: DistGraph, edge_attr=None) -> torch.Tensor:
+        if (edge_attr is None) != (self.edge_dim is None):
+            raise ValueError("edge_attr must be given exactly when edge_dim is set "
+                             f"(edge_dim={self.edge_dim})")
         xs = x if self.lin_src is None else self.lin_src(x)
-        msg = torch.relu(xs) + self.eps
-        h = dist_softmax_aggregate(msg, graph, self.t)
+        if edge_attr is None:
+            msg = torch.relu(xs) + self.eps
+            h = dist_softmax_aggregate(msg, graph, self.t)
+        else:
+            h = dist_softmax_aggregate_edge(xs, *self._edge_rows(edge_attr), graph, self.t,
+                                            relu=True, eps=self.eps)
         h = h + (x if self.lin_dst is None else self.lin_dst(x))
         return self.mlp(h)

@@ -13,6 +13,9 @@ def __getattr__(name):
     if name == "EdgeDrop":  # the DropEdge spec of aggregate(..., drop=)
         from .aggregate import EdgeDrop
         return EdgeDrop
+    if name == "softmax_aggregate_edge":  # softmax aggregation of per-edge messages
+        from .aggregate import softmax_aggregate_edge
+        return softmax_aggregate_edge
     if name == "gatv2_attention":
         from .gatv2 import gatv2_attention
         return gatv2_attention

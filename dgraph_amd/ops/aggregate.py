@@ -8,6 +8,9 @@
   rows in ONE gather pass (the PNA aggregators), as column blocks of one ``[R, A*F]`` tensor.
 * :func:`softmax_aggregate` — the learnable softmax aggregation (per channel, the score is
   the value times a temperature) in one gather pass, with the temperature's gradient.
+* :func:`softmax_aggregate_edge` — the same with a per-edge term in the message
+  (``relu(x_j + e_ij) + eps``, GENConv with edge features), formed inside the gather pass;
+  the backward writes the edge gradient once and sums it once for ``dx``.
 * :func:`gather` / :func:`scatter_sum` — vertex->edge gather and edge->vertex scatter-sum
   over a static :class:`~dgraph_amd.ops.csr.IndexMap`; each is the other's adjoint
   (the core contract of the reference, tests/test_NCCLCommPlan.py:100-111,297-307),
@@ -402,6 +405,70 @@ def edge_dot_grads(csr: CSR, a, b, w, heads: int, want_a: bool = True, want_b: b
         t = _slot_transpose(csr)
         db = K.spmm(t.rowptr, t.col, a, edge_weight=w[t.perm].contiguous(), heads=heads)
     return da, db
+
+
+# out-degree above which a source's de rows are summed as separate segment waves
+EDGE_SUM_HUB_CAP = 2048
+
+
+def sum_edge_rows(csr: CSR, de: torch.Tensor, out: Optional[torch.Tensor] = None,
+                  hub_cap: int = EDGE_SUM_HUB_CAP) -> torch.Tensor:
+    """``dx[c] = sum_{k: col[k] = c} de[k]``: the per-slot rows ``de`` (``[nnz, F]`` in
+    ``csr``'s slot order) summed per source, ``[csr.num_cols, F]``. A plain row-sum SpMM over
+    the slot-transposed pattern, whose slot map is the column array and ``de`` the source
+    matrix; a source of more than ``hub_cap`` entries is summed in segments."""
+    tt = _slot_transpose(csr)
+    return K.spmm(tt.rowptr, tt.perm, de, out, split=tt.hub_split(hub_cap))
+
+
+class _SoftmaxAggregateEdgeFn(Function):
+    """Softmax aggregation of per-edge messages (K.segment_softmax_edge). ``(out, lse)`` is
+    all the forward keeps beside its inputs; the backward recomputes every message and weight
+    in one pass over the same pattern, which writes ``de`` and the partial rows of ``dt``;
+    ``dx`` is the row sum of ``de`` over the slot-transposed pattern."""
+
+    @staticmethod
+    def forward(ctx, x, edge, t, csr: CSR, relu: bool, eps: float):
+        out, lse = K.segment_softmax_edge(csr.rowptr, csr.col, x, edge, t, relu=relu, eps=eps)
+        ctx.csr, ctx.relu, ctx.eps = csr, relu, eps
+        ctx.save_for_backward(x, edge, t, out, lse)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, edge, t, out, lse = ctx.saved_tensors
+        csr: CSR = ctx.csr
+        want_dt = ctx.needs_input_grad[2]
+        de, part = K.segment_softmax_edge_bwd(csr.rowptr, csr.col, x, edge, t, vec_rows(g), out,
+                                              lse, relu=ctx.relu, eps=ctx.eps, want_dt=want_dt)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dx = sum_edge_rows(csr, de)
+            if x.shape[0] != csr.num_cols:  # rows no column reaches
+                dx = torch.cat([dx, dx.new_zeros(x.shape[0] - csr.num_cols, dx.shape[1])])
+        return (dx, de if ctx.needs_input_grad[1] else None,
+                temperature_grad(part, t) if want_dt else None, None, None, None)
+
+
+def softmax_aggregate_edge(x: torch.Tensor, edge: torch.Tensor, csr: CSR, t=1.0,
+                           relu: bool = True, eps: float = 1e-7) -> torch.Tensor:
+    """Softmax aggregation of messages that depend on the edge (PyG's ``GENConv(edge_dim=)``
+    with ``aggr="softmax"``): for slot ``k`` of row ``r``, ``m_k = relu(x[col[k]] + edge[k]) +
+    eps`` (``relu=False``: no relu) and ``out[r, f] = sum_k softmax_k(t_f m_k) m_k`` (0 for an
+    empty row). ``edge`` is ``[csr.nnz, F]`` in the SLOT order of ``csr``; values in the order
+    of the edge list the CSR was built from go through ``csr.permute_edges`` first. ``t`` as in
+    :func:`softmax_aggregate`. Autograd covers ``x``, ``edge`` and ``t`` (a scalar receives the
+    sum of the per-channel gradient). On the GPU (fp32) one kernel forms every message in
+    registers between the gather and the softmax and writes nothing per edge; the backward
+    writes the edge gradient once and sums it once for ``dx``."""
+    if x.dim() != 2 or edge.dim() != 2 or tuple(edge.shape) != (csr.nnz, x.shape[1]):
+        raise ValueError(f"softmax_aggregate_edge: edge must be [{csr.nnz}, {x.shape[-1]}] in "
+                         f"csr's slot order, got {tuple(edge.shape)}")
+    if x.shape[0] < csr.num_cols:
+        raise ValueError(f"softmax_aggregate_edge: x has {x.shape[0]} rows, the pattern "
+                         f"{csr.num_cols} columns")
+    return _SoftmaxAggregateEdgeFn.apply(vec_rows(x), vec_rows(edge), as_temperature(t, x), csr,
+                                         bool(relu), float(eps))
 
 
 class _EdgeDotFn(Function):

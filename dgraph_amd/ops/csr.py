@@ -280,6 +280,18 @@ class CSR:
                              ncols, base_perm))
         return parts[0], parts[1]
 
+    def split_edge_values(self, boundary: int,
+                          values: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+        """Per-slot ``values`` (``[nnz, ...]`` in THIS CSR's slot order, e.g. after
+        :meth:`permute_edges`) as the two blocks of :meth:`split_columns` at ``boundary``:
+        ``(values of cols < boundary, values of cols >= boundary)``, each in its block's
+        slot order. A partition that keeps only the split blocks splits its edge attributes
+        with this before the unsplit CSR is dropped."""
+        if values.shape[0] != self.nnz:
+            raise ValueError(f"split_edge_values: {values.shape[0]} rows for {self.nnz} slots")
+        is_int = self.col.long() < boundary
+        return values[is_int], values[~is_int]
+
     def memory_bytes(self) -> int:
         n = self.rowptr.numel() * 8 + self.col.numel() * self.col.element_size()
         if self.perm is not None:

@@ -509,6 +509,135 @@ def segment_softmax_bwd(
     return dx, part
 
 
+def _check_edge_rows(name: str, x: torch.Tensor, e: torch.Tensor, col: torch.Tensor) -> None:
+    """The edge rows of :func:`segment_softmax_edge`: ``[nnz, F]`` of ``x``'s dtype (fp32 on
+    the GPU) on its device, unit column stride."""
+    F = x.shape[1]
+    if x.dim() != 2 or e.dim() != 2 or tuple(e.shape) != (col.numel(), F):
+        raise ValueError(f"{name}: e must be [{col.numel()}, {F}] (one row per CSR slot), got "
+                         f"{tuple(e.shape)}")
+    if e.dtype != x.dtype or e.device != x.device:
+        raise ValueError(f"{name}: e must be {x.dtype} on {x.device}, got {e.dtype} on "
+                         f"{e.device}")
+    if x.is_cuda and x.dtype != torch.float32:
+        raise ValueError(f"{name}: the GPU kernels are float32, got {x.dtype}")
+    for nm, v in (("x", x), ("e", e)):
+        if F > 1 and v.shape[0] > 0 and v.stride(1) != 1:
+            raise ValueError(f"{name}: {nm} must have unit column stride, got strides "
+                             f"{v.stride()}")
+
+
+def segment_softmax_edge_dt_parts(rows: int) -> int:
+    """The number of ``dt`` partial rows the GPU backward of :func:`segment_softmax_edge`
+    writes for a pattern of ``rows`` rows."""
+    return int(_native.ops().segment_softmax_edge_dt_parts(int(rows)))
+
+
+def segment_softmax_edge(
+    rowptr: torch.Tensor,
+    col: torch.Tensor,
+    x: torch.Tensor,
+    e: torch.Tensor,
+    t,
+    out: Optional[torch.Tensor] = None,
+    lse: Optional[torch.Tensor] = None,
+    *,
+    relu: bool = True,
+    eps: float = 1e-7,
+    second: bool = False,
+    row_map: Optional[torch.Tensor] = None,
+):
+    """Softmax aggregation of messages formed per edge, in ONE pass over the neighbour and
+    edge rows: for CSR slot ``k`` of row ``r``, ``z = x[col[k]] + e[k]`` and ``m_k = (relu ?
+    max(z, 0) : z) + eps`` (GENConv's message with edge features); ``out[r, f] = sum_k
+    softmax_k(t_f m_k) m_k`` and ``lse[r, f] = log sum_k exp(t_f m_k)`` (0 and ``-inf`` for an
+    empty row). ``e``: ``[nnz, F]``, one row per slot in slot order (its own row stride).
+    ``t``, ``second`` and ``row_map`` as in :func:`segment_softmax`. ``(out, lse)`` is the
+    whole state. Returns ``(out, lse)``."""
+    name = "segment_softmax_edge"
+    _check_edge_rows(name, x, e, col)
+    R = rowptr.numel() - 1
+    F = x.shape[1]
+    if (second or row_map is not None) and (out is None or lse is None):
+        raise ValueError(f"{name}: second / row_map need explicit out and lse")
+    t = temperature_rows(t, x, name)
+    if out is None:
+        out = torch.empty(R, F, dtype=x.dtype, device=x.device)
+    if lse is None:
+        lse = torch.empty(out.shape[0], F, dtype=x.dtype, device=x.device)
+    if row_map is None and (out.shape[0] < R or lse.shape[0] < R):
+        raise ValueError(f"{name}: out / lse need at least {R} rows, got {out.shape[0]} / "
+                         f"{lse.shape[0]}")
+    if _native_ok(x):
+        _native.ops().segment_softmax_edge_fwd(rowptr, col, x, e, t, out, lse, bool(relu),
+                                               float(eps), bool(second), row_map)
+        return out, lse
+    return _ref.segment_softmax_edge(rowptr, col, x, e, t, out, lse, bool(relu), float(eps),
+                                     second, row_map)
+
+
+def segment_softmax_edge_bwd(
+    rowptr: torch.Tensor,
+    col: torch.Tensor,
+    x: torch.Tensor,
+    e: torch.Tensor,
+    t,
+    g: torch.Tensor,
+    out_fwd: torch.Tensor,
+    lse: torch.Tensor,
+    de: Optional[torch.Tensor] = None,
+    *,
+    relu: bool = True,
+    eps: float = 1e-7,
+    want_dt: bool = True,
+    dt_partials: Optional[torch.Tensor] = None,
+):
+    """Destination-side backward of :func:`segment_softmax_edge`, over the SAME pattern (not
+    the transposed one) of ANY block of the entries, given the final ``(out_fwd, lse)``
+    (``g`` / ``out_fwd`` / ``lse`` indexed by the CSR row): per slot ``w = exp(t m - lse[r])``,
+    ``d = m - out_fwd[r]``, ``de[k] = w g[r] (1 + t d)`` where ``not relu`` or ``z > 0``, else
+    exactly 0 (``z == 0`` has gradient 0, as ``torch.relu``), and ``dt = sum_k w g[r] d^2``.
+    Every slot's row of ``de`` (``[>= nnz, F]``, own row stride; fresh when ``None``) is
+    written. ``dt`` comes as fixed-order partial rows ``[P, F]`` (``dt = partials.sum(0)``) in
+    ``dt_partials`` when given (the GPU needs ``P = segment_softmax_edge_dt_parts(rows)``),
+    else a fresh buffer; ``want_dt=False`` skips it and touches no buffer. The source side is
+    a row sum of ``de``: ``dx = spmm(tt.rowptr, tt.perm, de)`` over the slot-transposed
+    pattern ``tt``. No atomics. Returns ``(de, partials or None)``."""
+    name = "segment_softmax_edge_bwd"
+    _check_edge_rows(name, x, e, col)
+    R = rowptr.numel() - 1
+    F = x.shape[1]
+    nnz = col.numel()
+    t = temperature_rows(t, x, name)
+    if de is None:
+        de = torch.empty(nnz, F, dtype=x.dtype, device=x.device)
+    if de.dim() != 2 or de.shape[0] < nnz or de.shape[1] != F:
+        raise ValueError(f"{name}: de must be [>= {nnz}, {F}], got {tuple(de.shape)}")
+    for nm, v in (("g", g), ("out_fwd", out_fwd), ("lse", lse)):
+        if v.dim() != 2 or v.shape[0] < R or v.shape[1] != F:
+            raise ValueError(f"{name}: {nm} must be [>= {R}, {F}], got {tuple(v.shape)}")
+    if _native_ok(x):
+        ops = _native.ops()
+        part = None
+        if want_dt:
+            P = ops.segment_softmax_edge_dt_parts(R)
+            part = dt_partials if dt_partials is not None else torch.empty(
+                P, F, dtype=torch.float32, device=x.device)
+            if tuple(part.shape) != (P, F):
+                raise ValueError(f"{name}: dt_partials must be [{P}, {F}], got "
+                                 f"{tuple(part.shape)}")
+        ops.segment_softmax_edge_bwd(rowptr, col, x, e, t, g, out_fwd, lse, de, bool(relu),
+                                     float(eps), part)
+        return de, part
+    de, part = _ref.segment_softmax_edge_bwd(rowptr, col, x, e, t, g, out_fwd, lse, de,
+                                             bool(relu), float(eps), want_dt)
+    if part is not None and dt_partials is not None:
+        dt_partials.zero_()
+        dt_partials[:1] = part.to(dt_partials.dtype)
+        part = dt_partials
+    return de, part
+
+
 def copy_rows(
     x: torch.Tensor,
     src_idx: Optional[torch.Tensor] = None,

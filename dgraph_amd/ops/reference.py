@@ -335,6 +335,53 @@ def segment_softmax_bwd(t_rowptr, t_col, x, t, g, out_fwd, lse, dx, want_dt=True
     return dx, part
 
 
+def _edge_message(x, e, col, relu, eps, cdt):
+    """``(z, m)`` per CSR slot: ``z = x[col] + e`` and ``m = (relu ? max(z, 0) : z) + eps``."""
+    z = x.to(cdt)[col.long()] + e.to(cdt)
+    return z, (torch.relu(z) if relu else z) + eps
+
+
+def segment_softmax_edge(rowptr, col, x, e, t, out, lse, relu=True, eps=1e-7, second=False,
+                         row_map=None):
+    """Softmax aggregation of per-slot messages (cf. kernels.h): ``m_k = (relu ? max(z, 0) :
+    z) + eps`` with ``z = x[col[k]] + e[k]``, ``lse = log sum_k exp(t m_k)`` and ``out = sum_k
+    exp(t m_k - lse) m_k``. Empty rows, ``second`` and ``row_map`` as :func:`segment_softmax`,
+    which this is once the messages stand as the source rows of an identity column map."""
+    if rowptr.numel() - 1 <= 0 or x.shape[1] == 0:
+        return out, lse
+    cdt = torch.float64 if x.dtype == torch.float64 else torch.float32
+    _, m = _edge_message(x, e, col, relu, eps, cdt)
+    slots = torch.arange(col.numel(), device=col.device)
+    return segment_softmax(rowptr, slots, m, t, out, lse, second, row_map)
+
+
+def segment_softmax_edge_bwd(rowptr, col, x, e, t, g, out_fwd, lse, de, relu=True, eps=1e-7,
+                             want_dt=True):
+    """Destination-side backward of :func:`segment_softmax_edge` over any block of the
+    entries, given the final ``(out_fwd, lse)`` (cf. kernels.h): per slot ``w = exp(t m -
+    lse[r])``, ``d = m - out_fwd[r]``, ``de[k] = w g[r] (1 + t d)`` where ``!relu`` or ``z >
+    0`` (else 0), and the one partial row ``sum w g[r] d^2`` of ``dt``. Returns ``(de, [1, F]
+    partials or None)``."""
+    F = x.shape[1]
+    cdt = torch.float64 if x.dtype == torch.float64 else torch.float32
+    part = torch.zeros(1, F, dtype=cdt, device=x.device) if want_dt else None
+    nnz = col.numel()
+    if nnz == 0 or F == 0:
+        return de, part
+    r = _row_ids(rowptr)
+    tt = t.to(cdt)
+    z, m = _edge_message(x, e, col, relu, eps, cdt)
+    wg = torch.exp(tt * m - lse.to(cdt)[r]) * g.to(cdt)[r]
+    d = m - out_fwd.to(cdt)[r]
+    dm = wg * (1 + tt * d)
+    if relu:
+        dm = torch.where(z > 0, dm, torch.zeros((), dtype=cdt, device=x.device))
+    de[:nnz] = dm.to(de.dtype)
+    if want_dt:
+        part = (wg * d * d).sum(0, keepdim=True)
+    return de, part
+
+
 def copy_rows(
     x: torch.Tensor,
     src_idx: Optional[torch.Tensor],

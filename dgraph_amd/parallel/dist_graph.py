@@ -762,6 +762,151 @@ class DistGraph:
             K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
         return dx, dt
 
+    def _edge_blocks(self, e_int, e_halo, x: torch.Tensor, name: str):
+        """The per-slot edge rows of the two blocks, checked: ``e_int`` ``[interior.nnz, F]``
+        and ``e_halo`` ``[halo.nnz, F]`` (``None`` where the block has no entry)."""
+        F = x.shape[1]
+        blocks = []
+        for blk, e, nm in ((self.interior, e_int, "e_int"), (self.halo, e_halo, "e_halo")):
+            n = blk.nnz if blk is not None else 0
+            if e is None:
+                e = x.new_empty(0, F)
+            if e.dim() != 2 or tuple(e.shape) != (n, F):
+                raise ValueError(f"{name}: {nm} must be [{n}, {F}] (one row per slot of the "
+                                 f"block), got {tuple(e.shape)}")
+            blocks.append(vec_rows(e))
+        return blocks
+
+    def aggregate_softmax_edge(self, x: torch.Tensor, e_int: torch.Tensor,
+                               e_halo: Optional[torch.Tensor], t: torch.Tensor,
+                               relu: bool = True, eps: float = 1e-7,
+                               halo_rows: Optional[torch.Tensor] = None):
+        """Softmax aggregation of per-edge messages ``relu(x[j] + e_ij) + eps`` over the
+        in-neighbours, local and halo (:func:`~dgraph_amd.ops.kernels.segment_softmax_edge`),
+        on the schedule of :meth:`aggregate_softmax`: the exchange of the ``x`` send rows is
+        posted first, the interior block runs under it, then the halo block runs over all
+        ``L`` rows starting from the interior's ``(out, lse)``. The edge rows never travel:
+        ``e_int`` / ``e_halo`` are this rank's per-slot rows of ``self.interior`` /
+        ``self.halo`` (one block per CSR block, as :meth:`edge_dot` returns its scores;
+        :meth:`~dgraph_amd.ops.csr.CSR.split_edge_values` cuts per-slot values of the unsplit
+        pattern into them). ``t``: the ``[F]`` temperature. Returns ``(out, saved)`` with
+        ``saved`` as :meth:`aggregate_softmax`'s."""
+        self.edges_aggregated += self.nnz
+        L, F = self.L, x.shape[1]
+        it = self.interior
+        e_int, e_halo = self._edge_blocks(e_int, e_halo, x, "aggregate_softmax_edge")
+        out = torch.empty(L, F, dtype=x.dtype, device=x.device)
+        lse = torch.empty(L, F, dtype=x.dtype, device=x.device)
+        saved = dict(out=out, lse=lse, halo=None)
+        kw = dict(relu=relu, eps=eps)
+        if self.halo is None or halo_rows is not None:
+            K.segment_softmax_edge(it.rowptr, it.col, x, e_int, t, out, lse, **kw)
+            if self.halo is not None:
+                K.segment_softmax_edge(self.halo.rowptr, self.halo.col, halo_rows, e_halo, t,
+                                       out, lse, second=True, **kw)
+            saved["halo"] = halo_rows
+            return out, saved
+        # the exchanges depend on the plan alone (a rank with sends and no halo entry posts
+        # them too); column chunks as in aggregate()
+        pend = []
+        for c0, c1 in self._col_chunks(self.a2a, F, x.element_size()):
+            xc = x if (c0, c1) == (0, F) else x[:, c0:c1]
+            recv, work = self.a2a(K.gather_rows(xc, self.send_map.idx), async_op=True)
+            if not self.overlap:
+                work.wait()
+            pend.append((c0, c1, recv, work))
+        K.segment_softmax_edge(it.rowptr, it.col, x, e_int, t, out, lse, **kw)
+        for c0, c1, recv, work in pend:
+            work.wait()
+            whole = (c0, c1) == (0, F)
+            K.segment_softmax_edge(self.halo.rowptr, self.halo.col, recv,
+                                   e_halo if whole else e_halo[:, c0:c1],
+                                   t if whole else t[c0:c1],
+                                   out if whole else out[:, c0:c1],
+                                   lse if whole else lse[:, c0:c1], second=True, **kw)
+        saved["halo"] = pend[0][2] if len(pend) == 1 else torch.cat([p[2] for p in pend], 1)
+        return out, saved
+
+    def aggregate_softmax_edge_T(self, g: torch.Tensor, x: torch.Tensor, e_int: torch.Tensor,
+                                 e_halo: Optional[torch.Tensor], t: torch.Tensor, saved: dict,
+                                 relu: bool = True, eps: float = 1e-7,
+                                 out: Optional[torch.Tensor] = None,
+                                 halo_out: Optional[torch.Tensor] = None,
+                                 want_dt: bool = True):
+        """Backward of :meth:`aggregate_softmax_edge` (``g``: ``[L, F]``; the other arguments
+        are the forward's inputs and second result). Each block runs the destination-side
+        kernel over its own pattern with the final ``(out, lse)``, which writes the block's
+        edge gradient; the source gradient is the row sum of those rows over the block's
+        slot-transposed pattern. The halo block goes first: its sums are the ``[H, F]`` rows
+        that take the reverse path of :meth:`aggregate_softmax_T` (reverse exchange under the
+        interior block, owner-side segment sum). ``halo_out``: ``[H, F]`` buffer that keeps
+        the halo gradient here. Returns ``(dx, de_int, de_halo, dt)``; ``de_halo`` is ``[0,
+        F]`` without halo entries, and ``dt`` (``[F]``, or ``None`` without ``want_dt``) is
+        this rank's part, as :meth:`aggregate_softmax_T`'s."""
+        from ..ops.aggregate import sum_edge_rows
+
+        g = vec_rows(g)
+        F = x.shape[1]
+        it = self.interior
+        e_int, e_halo = self._edge_blocks(e_int, e_halo, x, "aggregate_softmax_edge_T")
+        self.edges_aggregated += self.nnz
+        of, lse = saved["out"], saved["lse"]
+        kw = dict(relu=relu, eps=eps, want_dt=want_dt)
+        dt = None
+
+        def add_dt(part, c0=0, c1=F):
+            nonlocal dt
+            if part is None:
+                return
+            if dt is None:
+                dt = torch.zeros(F, dtype=part.dtype, device=part.device)
+            dt[c0:c1] += part.sum(0)
+
+        def interior():
+            de, part = K.segment_softmax_edge_bwd(it.rowptr, it.col, x, e_int, t, g, of, lse,
+                                                  **kw)
+            add_dt(part)
+            return sum_edge_rows(it, de, out, SPMM_HUB_CAP), de
+
+        def halo_sum(de, into=None):
+            # [H, w]: a halo block without entries (a rank that only sends) sums to nothing
+            if self.halo.nnz == 0:
+                return de.new_zeros(self.H, de.shape[1]) if into is None else into.zero_()
+            return sum_edge_rows(self.halo, de, into, SPMM_HUB_CAP)
+
+        if self.halo is None:
+            dx, de_int = interior()
+            return dx, de_int, x.new_empty(0, F), dt
+        ht = self.halo
+        xh = saved["halo"]
+        de_halo = torch.empty(ht.nnz, F, dtype=x.dtype, device=x.device)
+        if halo_out is not None:
+            _, part = K.segment_softmax_edge_bwd(ht.rowptr, ht.col, xh, e_halo, t, g, of, lse,
+                                                 de_halo, **kw)
+            add_dt(part)
+            halo_sum(de_halo, halo_out)
+            dx, de_int = interior()
+            return dx, de_int, de_halo, dt
+        pend = []
+        for c0, c1 in self._col_chunks(self.a2a_rev, F, g.element_size()):
+            whole = (c0, c1) == (0, F)
+            cut = (lambda v: v) if whole else (lambda v: v[:, c0:c1])  # noqa: E731
+            dec, part = K.segment_softmax_edge_bwd(ht.rowptr, ht.col, cut(xh), cut(e_halo),
+                                                   t if whole else t[c0:c1], cut(g), cut(of),
+                                                   cut(lse), cut(de_halo), **kw)
+            add_dt(part, c0, c1)
+            sg, work = self.a2a_rev(halo_sum(dec), async_op=True)
+            if not self.overlap:
+                work.wait()
+            pend.append((c0, c1, sg, work))
+        dx, de_int = interior()
+        st = self.send_map.transpose_csr().compact_rows()
+        for c0, c1, sg, work in pend:
+            work.wait()
+            oc = dx if (c0, c1) == (0, F) else dx[:, c0:c1]
+            K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
+        return dx, de_int, de_halo, dt
+
     def edge_dot(self, a: torch.Tensor, b: torch.Tensor, heads: int = 1, scale: float = 1.0,
                  halo_rows: Optional[torch.Tensor] = None):
         """One score per edge at this rank's vertices, local and halo sources
@@ -1142,6 +1287,44 @@ def dist_softmax_aggregate(x: torch.Tensor, graph: DistGraph, t=1.0) -> torch.Te
     :meth:`DistGraph.aggregate_softmax`). ``t`` as there; its gradient is this rank's part
     (``t`` is a replicated parameter: all-reduce it with the other weight gradients)."""
     return _DistSoftmaxAggregateFn.apply(x, as_temperature(t, x), graph)
+
+
+class _DistSoftmaxAggregateEdgeFn(Function):
+    @staticmethod
+    def forward(ctx, x, e_int, e_halo, t, graph: DistGraph, relu: bool, eps: float):
+        x = vec_rows(x)
+        tv = K.temperature_rows(t, x, "dist_softmax_aggregate_edge")
+        out, saved = graph.aggregate_softmax_edge(x, e_int, e_halo, tv, relu, eps)
+        ctx.graph, ctx.relu, ctx.eps = graph, relu, eps
+        ctx.save_for_backward(x, e_int, e_halo, t, out, saved["lse"], saved["halo"])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        x, e_int, e_halo, t, out, lse, halo = ctx.saved_tensors
+        tv = K.temperature_rows(t, x, "dist_softmax_aggregate_edge")
+        want_dt = ctx.needs_input_grad[3]
+        dx, de_int, de_halo, dt = ctx.graph.aggregate_softmax_edge_T(
+            g, x, e_int, e_halo, tv, dict(out=out, lse=lse, halo=halo), ctx.relu, ctx.eps,
+            want_dt=want_dt)
+        if want_dt:
+            dt = (dt.sum() if t.numel() == 1 else dt).reshape(t.shape).to(t.dtype)
+        return (dx, de_int, None if e_halo is None else de_halo.reshape(e_halo.shape), dt,
+                None, None, None)
+
+
+def dist_softmax_aggregate_edge(x: torch.Tensor, e_int: torch.Tensor,
+                                e_halo: Optional[torch.Tensor], graph: DistGraph, t=1.0,
+                                relu: bool = True, eps: float = 1e-7) -> torch.Tensor:
+    """Autograd-aware distributed :func:`~dgraph_amd.ops.aggregate.softmax_aggregate_edge`:
+    the softmax aggregation of the messages ``relu(x[j] + e_ij) + eps`` over every local
+    vertex's in-neighbours, local and halo (one exchange of ``x`` rows forward, one backward;
+    :meth:`DistGraph.aggregate_softmax_edge`). ``e_int`` / ``e_halo``: the edge rows of
+    ``graph.interior`` / ``graph.halo`` in their slot order (``e_halo`` may be ``None`` when
+    the halo block has no entry). Gradients reach ``x``, both edge blocks and ``t``, whose
+    gradient is this rank's part, as :func:`dist_softmax_aggregate`'s."""
+    return _DistSoftmaxAggregateEdgeFn.apply(x, e_int, e_halo, as_temperature(t, x), graph,
+                                             bool(relu), float(eps))
 
 
 class _DistEdgeDotFn(Function):
