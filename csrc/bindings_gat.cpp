@@ -4,24 +4,16 @@
 // against the operand rows once per pattern by the Python caller (ops/gat.py).
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include "attn_check.h"
 #include "check.h"
 #include "kernels/kernels.h"
 
 namespace dgraph {
 namespace {
 
-hipStream_t cur_stream(const at::Tensor& t) {
-  return c10::hip::getCurrentHIPStream(t.device().index()).stream();
-}
-
-const at::Tensor* opt_t(const c10::optional<at::Tensor>& t) {
-  return (t.has_value() && t->defined()) ? &*t : nullptr;
-}
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+constexpr const char* kOp = "gat";  // the prefix of every message
 
 void rows_f32(const at::Tensor& t, const at::Tensor& ref, int64_t min_rows, int64_t cols,
               const char* name) {
@@ -48,17 +40,6 @@ void scores(const at::Tensor& t, const at::Tensor& ref, int64_t min_rows, int64_
               t.strides());
 }
 
-IType pattern(const at::Tensor& rowptr, const at::Tensor& col, const at::Tensor& ref) {
-  TORCH_CHECK(rowptr.is_cuda() && rowptr.device() == ref.device() &&
-                  rowptr.scalar_type() == at::kLong && rowptr.is_contiguous() &&
-                  rowptr.dim() == 1 && rowptr.numel() >= 1,
-              "gat: rowptr must be contiguous int64 on ", ref.device());
-  TORCH_CHECK(col.is_cuda() && col.device() == ref.device() && col.is_contiguous() &&
-                  (col.scalar_type() == at::kInt || col.scalar_type() == at::kLong),
-              "gat: col must be contiguous int32/int64 on ", ref.device());
-  return col.scalar_type() == at::kInt ? IType::I32 : IType::I64;
-}
-
 // sd/out rows = CSR rows; x (+ x2 past nsplit) = the gathered rows
 void gat_fwd_op(const at::Tensor& rowptr, const at::Tensor& col, const at::Tensor& x,
                 const c10::optional<at::Tensor>& x2, int64_t nsplit, const at::Tensor& ss,
@@ -66,7 +47,7 @@ void gat_fwd_op(const at::Tensor& rowptr, const at::Tensor& col, const at::Tenso
                 double beta, at::Tensor& stat_m, at::Tensor& stat_l, int64_t heads,
                 double slope) {
   const c10::DeviceGuard guard(x.device());
-  const IType it = pattern(rowptr, col, x);
+  const IType it = pattern(kOp, rowptr, col, x);
   const int64_t R = rowptr.numel() - 1;
   const int C = static_cast<int>(x.size(1));
   TORCH_CHECK(gat_f32_shape_ok(C, static_cast<int>(heads)), "gat: unsupported width ", C,
@@ -103,7 +84,7 @@ void gat_bwd_dst_op(const at::Tensor& rowptr, const at::Tensor& col, const at::T
                     const at::Tensor& stat_m, const at::Tensor& stat_l, const at::Tensor& g,
                     at::Tensor& c_out, at::Tensor& gsd_out, int64_t heads, double slope) {
   const c10::DeviceGuard guard(x.device());
-  const IType it = pattern(rowptr, col, x);
+  const IType it = pattern(kOp, rowptr, col, x);
   const int64_t R = rowptr.numel() - 1;
   const int C = static_cast<int>(x.size(1));
   TORCH_CHECK(gat_f32_shape_ok(C, static_cast<int>(heads)), "gat: unsupported width / heads");
@@ -143,7 +124,7 @@ void gat_bwd_src_op(const at::Tensor& rowptr, const at::Tensor& col, const at::T
                     const at::Tensor& a_src, at::Tensor& gz,
                     const c10::optional<at::Tensor>& gss, int64_t heads, double slope) {
   const c10::DeviceGuard guard(g.device());
-  const IType it = pattern(rowptr, col, g);
+  const IType it = pattern(kOp, rowptr, col, g);
   const int64_t R = rowptr.numel() - 1;
   const int C = static_cast<int>(g.size(1));
   TORCH_CHECK(gat_f32_shape_ok(C, static_cast<int>(heads)), "gat: unsupported width / heads");

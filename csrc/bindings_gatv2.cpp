@@ -11,64 +11,16 @@
 // launched kernel gathers from always exists.
 #include <ATen/ATen.h>
 #include <c10/core/DeviceGuard.h>
-#include <c10/hip/HIPStream.h>
 #include <torch/library.h>
 
+#include "attn_check.h"
 #include "check.h"
 #include "kernels/kernels.h"
 
 namespace dgraph {
 namespace {
 
-hipStream_t cur_stream(const at::Tensor& t) {
-  return c10::hip::getCurrentHIPStream(t.device().index()).stream();
-}
-
-const at::Tensor* opt_t(const c10::optional<at::Tensor>& t) {
-  return (t.has_value() && t->defined()) ? &*t : nullptr;
-}
-
-bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
-// a feature array: [>= min_rows, C] float32, unit column stride, 16-B aligned rows
-void rows_f32(const at::Tensor& t, const at::Tensor& ref, int64_t min_rows, int64_t cols,
-              const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.device() == ref.device(), "gatv2: ", name, " must be on ",
-              ref.device());
-  TORCH_CHECK(t.scalar_type() == at::kFloat && t.dim() == 2 && t.size(1) == cols &&
-                  t.size(0) >= min_rows,
-              "gatv2: ", name, " must be float32 [>= ", min_rows, ", ", cols, "], got ",
-              t.sizes());
-  if (t.size(0) == 0) return;
-  TORCH_CHECK(t.stride(1) == 1 && t.stride(0) % 4 == 0 && t.stride(0) >= cols &&
-                  al16(t.data_ptr()),
-              "gatv2: ", name, " must have unit column stride, a row stride divisible by 4 "
-              "and 16-B alignment, got strides ", t.strides());
-}
-
-// per-head arrays: [>= min_rows, heads] with unit column stride and the shared row stride
-void per_head(const at::Tensor& t, const at::Tensor& ref, int64_t min_rows, int64_t heads,
-              int64_t lds, const char* name) {
-  TORCH_CHECK(t.is_cuda() && t.device() == ref.device() && t.scalar_type() == at::kFloat &&
-                  t.dim() == 2 && t.size(1) == heads && t.size(0) >= min_rows,
-              "gatv2: ", name, " must be float32 [>= ", min_rows, ", ", heads, "] on ",
-              ref.device(), ", got ", t.sizes());
-  if (t.size(0) == 0) return;
-  TORCH_CHECK((heads == 1 || t.stride(1) == 1) && t.stride(0) == lds && lds >= heads,
-              "gatv2: ", name, " must have unit column stride and row stride ", lds,
-              ", got strides ", t.strides());
-}
-
-IType pattern(const at::Tensor& rowptr, const at::Tensor& col, const at::Tensor& ref) {
-  TORCH_CHECK(rowptr.is_cuda() && rowptr.device() == ref.device() &&
-                  rowptr.scalar_type() == at::kLong && rowptr.is_contiguous() &&
-                  rowptr.dim() == 1 && rowptr.numel() >= 1,
-              "gatv2: rowptr must be contiguous int64 on ", ref.device());
-  TORCH_CHECK(col.is_cuda() && col.device() == ref.device() && col.is_contiguous() &&
-                  (col.scalar_type() == at::kInt || col.scalar_type() == at::kLong),
-              "gatv2: col must be contiguous int32/int64 on ", ref.device());
-  return col.scalar_type() == at::kInt ? IType::I32 : IType::I64;
-}
+constexpr const char* kOp = "gatv2";  // the prefix of every message
 
 int width(const at::Tensor& xd, int64_t heads) {
   TORCH_CHECK(xd.is_cuda() && xd.dim() == 2, "gatv2: xd must be a 2-D device tensor");
@@ -97,7 +49,7 @@ struct Sources {
 
 Sources sources(const at::Tensor& xd, const at::Tensor& xs,
                 const c10::optional<at::Tensor>& xs2, int64_t nsplit, int C) {
-  rows_f32(xs, xd, 0, C, "xs");
+  rows_f32(kOp, xs, xd, 0, C, "xs");
   const at::Tensor* p2 = opt_t(xs2);
   TORCH_CHECK(nsplit >= 0 && nsplit < (int64_t(1) << 32), "gatv2: bad nsplit");
   Sources s;
@@ -105,7 +57,7 @@ Sources sources(const at::Tensor& xd, const at::Tensor& xs,
   s.ldxs = xs.stride(0);
   s.rows = xs.size(0);
   if (p2) {
-    rows_f32(*p2, xd, 0, C, "xs2");
+    rows_f32(kOp, *p2, xd, 0, C, "xs2");
     TORCH_CHECK(xs.size(0) >= nsplit, "gatv2: xs has fewer rows than nsplit");
     if (p2->size(0) > 0) {
       s.xs2 = p2->data_ptr<float>();
@@ -124,15 +76,15 @@ void gatv2_fwd_op(const at::Tensor& rowptr, const at::Tensor& col, const at::Ten
                   at::Tensor& stat_l, int64_t heads, double slope) {
   const c10::DeviceGuard guard(xd.device());
   const int C = width(xd, heads);
-  const IType it = pattern(rowptr, col, xd);
+  const IType it = pattern(kOp, rowptr, col, xd);
   const int64_t R = rowptr.numel() - 1;
   const int64_t lds = stat_m.dim() == 2 ? stat_m.stride(0) : 0;
-  rows_f32(xd, xd, R, C, "xd");
+  rows_f32(kOp, xd, xd, R, C, "xd");
   const Sources s = sources(xd, xs, xs2, nsplit, C);
   const float* ap = att_vec(att, xd, C);
-  rows_f32(out, xd, R, C, "out");
-  per_head(stat_m, xd, R, heads, lds, "stat_m");
-  per_head(stat_l, xd, R, heads, lds, "stat_l");
+  rows_f32(kOp, out, xd, R, C, "out");
+  per_head(kOp, stat_m, xd, R, heads, lds, "stat_m");
+  per_head(kOp, stat_l, xd, R, heads, lds, "stat_l");
   if (R == 0) return;
   if (s.rows == 0) {  // nothing to gather from: every row is empty
     TORCH_CHECK(col.numel() == 0, "gatv2: entries but no source rows");
@@ -157,17 +109,17 @@ void gatv2_bwd_dst_op(const at::Tensor& rowptr, const at::Tensor& col, const at:
                       at::Tensor& dxd, at::Tensor& da_part, int64_t heads, double slope) {
   const c10::DeviceGuard guard(xd.device());
   const int C = width(xd, heads);
-  const IType it = pattern(rowptr, col, xd);
+  const IType it = pattern(kOp, rowptr, col, xd);
   const int64_t R = rowptr.numel() - 1;
   const int64_t lds = stat_m.dim() == 2 ? stat_m.stride(0) : 0;
-  rows_f32(xd, xd, R, C, "xd");
+  rows_f32(kOp, xd, xd, R, C, "xd");
   const Sources s = sources(xd, xs, xs2, nsplit, C);
   const float* ap = att_vec(att, xd, C);
-  per_head(stat_m, xd, R, heads, lds, "stat_m");
-  per_head(stat_l, xd, R, heads, lds, "stat_l");
-  per_head(c, xd, R, heads, lds, "c");
-  rows_f32(g, xd, R, C, "g");
-  rows_f32(dxd, xd, R, C, "dxd");
+  per_head(kOp, stat_m, xd, R, heads, lds, "stat_m");
+  per_head(kOp, stat_l, xd, R, heads, lds, "stat_l");
+  per_head(kOp, c, xd, R, heads, lds, "c");
+  rows_f32(kOp, g, xd, R, C, "g");
+  rows_f32(kOp, dxd, xd, R, C, "dxd");
   const int64_t P = gatv2_da_parts(R, C);
   TORCH_CHECK(da_part.is_cuda() && da_part.device() == xd.device() &&
                   da_part.scalar_type() == at::kFloat && da_part.dim() == 2 &&
@@ -198,18 +150,18 @@ void gatv2_bwd_src_op(const at::Tensor& rowptr, const at::Tensor& col, const at:
                       at::Tensor& dxs, int64_t heads, double slope) {
   const c10::DeviceGuard guard(xd.device());
   const int C = width(xd, heads);
-  const IType it = pattern(rowptr, col, xd);
+  const IType it = pattern(kOp, rowptr, col, xd);
   const int64_t R = rowptr.numel() - 1;
   const int64_t nd = xd.size(0);
   const int64_t lds = stat_m.dim() == 2 ? stat_m.stride(0) : 0;
-  rows_f32(xd, xd, 0, C, "xd");
-  rows_f32(g, xd, nd, C, "g");
+  rows_f32(kOp, xd, xd, 0, C, "xd");
+  rows_f32(kOp, g, xd, nd, C, "g");
   const float* ap = att_vec(att, xd, C);
-  per_head(stat_m, xd, nd, heads, lds, "stat_m");
-  per_head(stat_l, xd, nd, heads, lds, "stat_l");
-  per_head(c, xd, nd, heads, lds, "c");
-  rows_f32(xs, xd, R, C, "xs");
-  rows_f32(dxs, xd, R, C, "dxs");
+  per_head(kOp, stat_m, xd, nd, heads, lds, "stat_m");
+  per_head(kOp, stat_l, xd, nd, heads, lds, "stat_l");
+  per_head(kOp, c, xd, nd, heads, lds, "c");
+  rows_f32(kOp, xs, xd, R, C, "xs");
+  rows_f32(kOp, dxs, xd, R, C, "dxs");
   if (R == 0) return;
   if (nd == 0) {  // no destination rows: no entries, every source row's gradient is 0
     TORCH_CHECK(col.numel() == 0, "gatv2: entries but no destination rows");

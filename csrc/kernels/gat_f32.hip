@@ -27,7 +27,7 @@
 // concatenated. Layout: one LPR-lane group per row (LPR = C / 4, 16-B fp32 vectors), the HH
 // heads as contiguous lane blocks of LH = LPR / HH lanes. Fixed summation orders, no atomics:
 // bitwise deterministic.
-#include "../common.h"
+#include "attn_device.h"
 #include "kernels.h"
 
 namespace dgraph {
@@ -84,14 +84,6 @@ __device__ __forceinline__ int64_t load_col(const GatArgs& a, int64_t pos) {
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
-// sum over the LH lanes of one head (contiguous, aligned lane blocks)
-template <int LH>
-__device__ __forceinline__ float head_sum(float v) {
-#pragma unroll
-  for (int off = LH / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 // reduce over the LPR lanes of a row group
 template <int LPR>
 __device__ __forceinline__ float group_max(float v) {
@@ -105,16 +97,6 @@ __device__ __forceinline__ float group_sum(float v) {
   for (int off = LPR / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
   return v;
 }
-template <int LPR>
-__device__ __forceinline__ int group_imax(int v) {
-#pragma unroll
-  for (int off = LPR; off < kWave; off <<= 1) {
-    const int o = __shfl_xor(v, off, kWave);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // ------------------------------------------------------------------------------------ fwd
 template <typename IdxT, int LPR, int HH>
 __global__ __launch_bounds__(256) void gat_fwd_kernel(GatArgs a) {

@@ -53,7 +53,7 @@
 // kU = 4 in gatv2_bwd_dst alone it takes 88 .. 97 VGPRs (occupancy 4 .. 5, no scalar
 // register moved) and on an MI355X measures the same within 2 % (PERFORMANCE.md): the depth
 // is not what bounds it, so one kU = 8 stays for all three, as in dot_attn_f32.hip.
-#include "../common.h"
+#include "attn_device.h"
 #include "kernels.h"
 
 namespace dgraph {
@@ -95,48 +95,6 @@ struct V2Args {
 template <typename IdxT>
 __device__ __forceinline__ int64_t load_col(const V2Args& a, int64_t pos) {
   return static_cast<int64_t>(static_cast<const IdxT*>(a.col)[pos]);
-}
-
-// sum over the LH lanes of one head (contiguous, aligned lane blocks); the same in all of them
-template <int LH>
-__device__ __forceinline__ float head_sum(float v) {
-#pragma unroll
-  for (int off = LH / 2; off >= 1; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
-// the longest row among the wave's row groups
-template <int LPR>
-__device__ __forceinline__ int group_imax(int v) {
-#pragma unroll
-  for (int off = LPR; off < kWave; off <<= 1) {
-    const int o = __shfl_xor(v, off, kWave);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
-__device__ __forceinline__ float dot4(const float4& a, const float4& b) {
-  float p = a.x * b.x;
-  p = fmaf(a.y, b.y, p);
-  p = fmaf(a.z, b.z, p);
-  return fmaf(a.w, b.w, p);
-}
-
-__device__ __forceinline__ void axpy4(float w, const float4& x, float4& acc) {
-  acc.x = fmaf(w, x.x, acc.x);
-  acc.y = fmaf(w, x.y, acc.y);
-  acc.z = fmaf(w, x.z, acc.z);
-  acc.w = fmaf(w, x.w, acc.w);
-}
-
-__device__ __forceinline__ const float4* vec(const float* p) {
-  return reinterpret_cast<const float4*>(p);
-}
-
-// pre = l + r: one add, the same bits whichever operand is the resident one
-__device__ __forceinline__ float4 add4(const float4& l, const float4& r) {
-  return make_float4(l.x + r.x, l.y + r.y, l.z + r.z, l.w + r.w);
 }
 
 __device__ __forceinline__ float4 leaky4(const float4& pre, float slope) {

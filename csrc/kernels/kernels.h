@@ -476,119 +476,88 @@ hipError_t gat_bwd_src_f32(IType it, const int64_t* rowptr, const void* col, int
                            hipStream_t st);
 
 // ---------------------------------------------------------------------------
-// Fused fp32 scaled dot-product graph attention of one relation (dot_attn_f32.hip):
+// Fused fp32 scaled dot-product graph attention of one relation (dot_attn_f32.h):
 // e_ij = scale <q_i, k_j> per head, softmax over each destination row's edges, the weighted
 // gather of v_j, and the exact adjoint (destination side: dq; source side over the
 // transposed pattern: dk and dv). Two sources: columns >= nsplit read k2 / v2. Every
 // feature array has its own row stride (floats); stat_m / stat_l / c share `lds`. A launch
 // needs row 0 of q and of the first gathered source to exist (padding slots read them).
+//
+// Variants of the same three kernels (formulas in dot_attn_f32.h):
+// * Carry (forward only): starts from the rows' carried softmax state instead of (0, -inf,
+//   0): on entry stat_l = 1 / sum of the earlier passes (0: nothing yet; out and stat_m are
+//   then not read), out their normalised result and stat_m their maximum; on return the
+//   three hold the softmax over the union of the earlier passes' entries and this pattern's.
+//   Rows without entries in this pattern are left bitwise untouched (their q is not read).
+//   No beta.
+// * Edge (TransformerConv with edge_dim): kk = k_j + ee_p, vv = v_j + ee_p with p the entry's
+//   CSR slot. ee [E, C] is read in slot order. The destination side also writes the per-edge
+//   gradient dee [E, C] and, per slot and head, w [E, 2 heads] = (alpha | de without scale):
+//   every real slot has exactly one writer, so dee and w need no initialisation. The source
+//   side reads only q, g and w (no lds, k, v, statistics), whose entry p' finds its weights
+//   at row t_slot[p'] of w. A launch also needs row 0 of ee and of w to exist.
+// * Drop (TransformerConv(dropout=p) in training): dropout on the attention coefficients
+//   after the softmax, mm = keep / (1 - p) with keep(slot, head) the Philox4x32-10 decision
+//   of philox.h. stat_m / stat_l are the plain forward's. The mask is never stored: every
+//   kernel regenerates it from (*seed, CSR slot, head); the source side finds the slot of
+//   transposed entry p' at t_slot[p']. No beta and no carry.
 bool dot_attn_f32_shape_ok(int C, int heads);
-hipError_t dot_attn_fwd_f32(IType it, const int64_t* rowptr, const void* col, int64_t nrows,
-                            int C, int heads, int64_t lds, float scale, const float* q,
-                            int64_t ldq, const float* k, int64_t ldk, const float* v,
-                            int64_t ldv, const float* k2, int64_t ldk2, const float* v2,
-                            int64_t ldv2, int64_t nsplit, float* out, int64_t ldo, float beta,
-                            float* stat_m, float* stat_l, hipStream_t st);
-// The forward started from the rows' carried softmax state instead of (0, -inf, 0): on entry
-// stat_l = 1 / sum of the earlier passes (0: nothing yet; out and stat_m are then not read),
-// out their normalised result and stat_m their maximum; on return the three hold the
-// softmax over the union of the earlier passes' entries and this pattern's. Rows without
-// entries in this pattern are left bitwise untouched (their q is not read).
-hipError_t dot_attn_fwd_carry_f32(IType it, const int64_t* rowptr, const void* col,
-                                  int64_t nrows, int C, int heads, int64_t lds, float scale,
-                                  const float* q, int64_t ldq, const float* k, int64_t ldk,
-                                  const float* v, int64_t ldv, const float* k2, int64_t ldk2,
-                                  const float* v2, int64_t ldv2, int64_t nsplit, float* out,
-                                  int64_t ldo, float* stat_m, float* stat_l, hipStream_t st);
-hipError_t dot_attn_bwd_dst_f32(IType it, const int64_t* rowptr, const void* col,
-                                int64_t nrows, int C, int heads, int64_t lds, float scale,
-                                const float* q, int64_t ldq, const float* k, int64_t ldk,
-                                const float* v, int64_t ldv, const float* k2, int64_t ldk2,
-                                const float* v2, int64_t ldv2, int64_t nsplit,
-                                const float* stat_m, const float* stat_l, const float* g,
-                                int64_t ldg, const float* c, float* dq, int64_t lddq,
-                                hipStream_t st);
-// rows = source rows (k / v resident); col = destination ids (q, g, stat_m, stat_l, c rows)
-hipError_t dot_attn_bwd_src_f32(IType it, const int64_t* rowptr, const void* col,
-                                int64_t nrows, int C, int heads, int64_t lds, float scale,
-                                const float* q, int64_t ldq, const float* g, int64_t ldg,
-                                const float* k, int64_t ldk, const float* v, int64_t ldv,
-                                const float* stat_m, const float* stat_l, const float* c,
-                                float* dk, int64_t lddk, float* dv, int64_t lddv,
-                                hipStream_t st);
 
-// ---------------------------------------------------------------------------
-// The same attention with a per-edge term in key and value (dot_attn_edge_f32.hip; PyG's
-// TransformerConv with edge_dim): kk = k_j + ee_p, vv = v_j + ee_p with p the entry's CSR
-// slot, then as above with kk / vv for k_j / v_j. ee [E, C] is read in slot order (a row's
-// slots are consecutive rows of ee). The destination side also writes the per-edge gradient
-// dee [E, C] and, per slot and head, w [E, 2 heads] = (alpha | de without scale): every real
-// slot has exactly one writer, so dee and w need no initialisation. The source side reads
-// only q, g and w: dv_j = sum alpha g_i, dk_j = scale sum de q_i over the transposed
-// pattern, whose entry p' finds its weights at row t_slot[p'] of w (t_slot has col's index
-// type and is indexed by absolute position, as col is). A launch needs row 0 of q, of the
-// first gathered source, of ee and of w to exist (padding slots read them with weight 0).
-hipError_t dot_attn_edge_fwd_f32(IType it, const int64_t* rowptr, const void* col,
-                                 int64_t nrows, int C, int heads, int64_t lds, float scale,
-                                 const float* q, int64_t ldq, const float* k, int64_t ldk,
-                                 const float* v, int64_t ldv, const float* k2, int64_t ldk2,
-                                 const float* v2, int64_t ldv2, int64_t nsplit,
-                                 const float* ee, int64_t ldee, float* out, int64_t ldo,
-                                 float beta, float* stat_m, float* stat_l, hipStream_t st);
-hipError_t dot_attn_edge_bwd_dst_f32(IType it, const int64_t* rowptr, const void* col,
-                                     int64_t nrows, int C, int heads, int64_t lds, float scale,
-                                     const float* q, int64_t ldq, const float* k, int64_t ldk,
-                                     const float* v, int64_t ldv, const float* k2,
-                                     int64_t ldk2, const float* v2, int64_t ldv2,
-                                     int64_t nsplit, const float* ee, int64_t ldee,
-                                     const float* stat_m, const float* stat_l, const float* g,
-                                     int64_t ldg, const float* c, float* dq, int64_t lddq,
-                                     float* dee, int64_t lddee, float* w, int64_t ldw,
-                                     hipStream_t st);
-// rows = source rows; col = destination ids (q, g rows); t_slot = forward slots (w rows)
-hipError_t dot_attn_edge_bwd_src_f32(IType it, const int64_t* rowptr, const void* col,
-                                     const void* t_slot, int64_t nrows, int C, int heads,
-                                     float scale, const float* q, int64_t ldq, const float* g,
-                                     int64_t ldg, const float* w, int64_t ldw, float* dk,
-                                     int64_t lddk, float* dv, int64_t lddv, hipStream_t st);
+// The operands of every kernel of the family; a caller fills what its kernel reads and
+// leaves the rest zero.
+struct DotAttnArgs {
+  const int64_t* rowptr;
+  const void* col;
+  const void* t_slot;  // bwd_src, Edge / Drop: forward slot of each transposed entry (col's
+                       // index type, indexed by absolute position as col is)
+  int64_t nrows;
+  int C;
+  float scale;
+  int64_t lds;       // row stride (floats) of stat_m / stat_l / c
+  const float* q;    // fwd / bwd_dst: the rows' own q; bwd_src: gathered by destination id
+  int64_t ldq;
+  const float* k;    // fwd / bwd_dst: gathered (columns < nsplit); bwd_src: the rows' own
+  int64_t ldk;
+  const float* v;
+  int64_t ldv;
+  const float* k2;   // second source (columns >= nsplit) or nullptr
+  int64_t ldk2;
+  const float* v2;
+  int64_t ldv2;
+  int64_t nsplit;
+  const float* ee;   // Edge: [E, C] by CSR slot
+  int64_t ldee;
+  float* out;        // fwd
+  int64_t ldo;
+  float beta;        // fwd, Plain / Edge
+  float* stat_m;     // [*, heads] written by fwd, read by the backward kernels
+  float* stat_l;
+  const float* g;    // dL/dout: bwd_dst the rows' own, bwd_src gathered
+  int64_t ldg;
+  const float* c;    // [*, heads] <g_i^h, o_i^h>
+  float* dq;         // bwd_dst
+  int64_t lddq;
+  float* dee;        // Edge bwd_dst: [E, C] by CSR slot
+  int64_t lddee;
+  float* w;          // Edge: [E, 2 heads] (alpha | de): written by bwd_dst, read by bwd_src
+  int64_t ldw;
+  float* dk;         // bwd_src (rows = source rows, col = destination ids)
+  int64_t lddk;
+  float* dv;
+  int64_t lddv;
+  const int64_t* seed;  // Drop: one int64 in device memory (read by the kernels, so a
+                        // captured step can refresh it per replay); must not be null
+  uint32_t thr;         // Drop: floor(p 2^32); keep when the head's Philox word >= thr
+  float inv_keep;       // Drop: 1 / (1 - p)
+};
 
-// ---------------------------------------------------------------------------
-// The same attention with dropout on the attention coefficients (dot_attn_drop_f32.hip; PyG's
-// TransformerConv(dropout=p) in training), applied after the softmax: mm = keep / (1 - p)
-// with keep(slot, head) the Philox4x32-10 decision of philox.h, out = sum alpha mm v,
-// de = alpha (mm ga - c), dv = sum alpha mm g. stat_m / stat_l are the plain forward's. The
-// mask is never stored: every kernel regenerates it from (*seed, CSR slot, head); the source
-// side finds the slot of transposed entry p' at t_slot[p'] (col's index type, indexed by
-// absolute position, as col is). seed points to ONE int64 in device memory (read by the
-// kernels, so a captured step can refresh it per replay); thr = floor(p 2^32);
-// inv_keep = 1 / (1 - p). No beta and no carry. Launch conditions as dot_attn_*_f32.
-hipError_t dot_attn_drop_fwd_f32(IType it, const int64_t* rowptr, const void* col,
-                                 int64_t nrows, int C, int heads, int64_t lds, float scale,
-                                 const float* q, int64_t ldq, const float* k, int64_t ldk,
-                                 const float* v, int64_t ldv, const float* k2, int64_t ldk2,
-                                 const float* v2, int64_t ldv2, int64_t nsplit, float* out,
-                                 int64_t ldo, float* stat_m, float* stat_l,
-                                 const int64_t* seed, uint32_t thr, float inv_keep,
-                                 hipStream_t st);
-hipError_t dot_attn_drop_bwd_dst_f32(IType it, const int64_t* rowptr, const void* col,
-                                     int64_t nrows, int C, int heads, int64_t lds, float scale,
-                                     const float* q, int64_t ldq, const float* k, int64_t ldk,
-                                     const float* v, int64_t ldv, const float* k2,
-                                     int64_t ldk2, const float* v2, int64_t ldv2,
-                                     int64_t nsplit, const float* stat_m, const float* stat_l,
-                                     const float* g, int64_t ldg, const float* c, float* dq,
-                                     int64_t lddq, const int64_t* seed, uint32_t thr,
-                                     float inv_keep, hipStream_t st);
-// rows = source rows (k / v resident); col = destination ids; t_slot = forward slots
-hipError_t dot_attn_drop_bwd_src_f32(IType it, const int64_t* rowptr, const void* col,
-                                     const void* t_slot, int64_t nrows, int C, int heads,
-                                     int64_t lds, float scale, const float* q, int64_t ldq,
-                                     const float* g, int64_t ldg, const float* k, int64_t ldk,
-                                     const float* v, int64_t ldv, const float* stat_m,
-                                     const float* stat_l, const float* c, float* dk,
-                                     int64_t lddk, float* dv, int64_t lddv,
-                                     const int64_t* seed, uint32_t thr, float inv_keep,
-                                     hipStream_t st);
+enum class DotKind : int { Fwd = 0, BwdDst = 1, BwdSrc = 2 };
+enum class DotVariant : int { Plain = 0, Carry = 1, Edge = 2, Drop = 3 };
+
+// Launches one kernel. nrows <= 0 launches nothing; an unsupported (C, heads), Carry with a
+// backward kind or Drop without a seed is hipErrorInvalidValue.
+hipError_t dot_attn_launch(DotKind kind, DotVariant variant, IType it, int heads,
+                           const DotAttnArgs& a, hipStream_t st);
 
 // ---------------------------------------------------------------------------
 // Fused fp32 GATv2 graph attention of one relation (gatv2_f32.hip):

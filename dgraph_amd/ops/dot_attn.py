@@ -12,7 +12,7 @@ read them as two sources (never concatenated), each with its own row stride, so 
 communication: the caller exchanges the halo rows (models/transformer_conv.py).
 
 GPU (fp32, C in 64/128/256, heads in 1/2/4/8 with C / heads >= 8): the three kernels of
-csrc/kernels/dot_attn_f32.hip — forward with a running maximum (k_j and v_j gathered once,
+csrc/kernels/dot_attn_f32.h — forward with a running maximum (k_j and v_j gathered once,
 nothing per edge stored), backward destination side (``dq``), backward source side over the
 transposed pattern (``dk``, ``dv``; once for the local rows, once for the halo rows). The
 backward's ``c_i = <g_i, out_i>`` per head is one elementwise pass over the saved output.
@@ -20,8 +20,8 @@ Anything else on the GPU raises ``ValueError``. CPU: the same math in plain PyTo
 autograd at fp64 (the numerics oracle), returned in the input dtype.
 
 With ``edge=`` (``[E, C]``, one row per CSR slot, added to the edge's key and value) the op
-runs the three kernels of csrc/kernels/dot_attn_edge_f32.hip instead: the forward and the
-destination side stream the edge rows in slot order, the destination side writes the per-edge
+runs the edge variant of the three kernels (csrc/kernels/dot_attn_edge_f32.hip) instead: the
+forward and the destination side stream the edge rows in slot order, the destination side writes the per-edge
 gradient and two weights per slot and head, and the source side reads those weights through
 ``GatPattern.t_slot``. :func:`dot_attention_parts` / :func:`dot_attention_halo` take no edge
 features.
@@ -102,15 +102,41 @@ def _rows(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     return t.contiguous()
 
 
+def _out_stats(R: int, C: int, heads: int, device):
+    """The forward's ``out [R, C]`` and statistics ``m``, ``l`` ``[R, heads]``, uninitialised."""
+    out = torch.empty(R, C, dtype=torch.float32, device=device)
+    m = torch.empty(R, heads, dtype=torch.float32, device=device)
+    return out, m, torch.empty_like(m)
+
+
+def _src_side(pat: GatPattern, k, v, kh, vh, bwd_src):
+    """``dk, dv, dkh, dvh`` of the backward's source side: the local rows, then the halo rows
+    over the tail of the transposed row pointer. ``bwd_src(t_rowptr, k, v, dk, dv)`` runs one
+    side's kernel. Rows past the pattern's columns have no entries: their gradient is zero
+    (``zeros``; ``empty`` when the kernel writes every row)."""
+    C = k.shape[1]
+
+    def side(t_rowptr, ks, vs, ncol):
+        alloc = torch.empty if ks.shape[0] == ncol else torch.zeros
+        dks = alloc(ks.shape[0], C, dtype=torch.float32, device=ks.device)
+        dvs = alloc(ks.shape[0], C, dtype=torch.float32, device=ks.device)
+        bwd_src(t_rowptr, ks, vs, dks, dvs)
+        return dks, dvs
+
+    if kh is None:
+        nloc = pat.nsplit + pat.H
+        return (*side(pat.t_rowptr[:nloc + 1], k, v, nloc), None, None)
+    return (*side(pat.t_rowptr[:pat.nsplit + 1], k, v, pat.nsplit),
+            *side(pat.t_rowptr[pat.nsplit:], kh, vh, pat.H))
+
+
 class _DotAttnFn(Function):
     @staticmethod
     def forward(ctx, q, k, v, kh, vh, pat: GatPattern, heads: int, scale: float):
         ops = _native.ops()
         q, k, v, kh, vh = (_rows(t) for t in (q, k, v, kh, vh))
         R, C = pat.R, q.shape[1]
-        out = torch.empty(R, C, dtype=torch.float32, device=q.device)
-        m = torch.empty(R, heads, dtype=torch.float32, device=q.device)
-        l = torch.empty_like(m)
+        out, m, l = _out_stats(R, C, heads, q.device)
         ops.dot_attn_fwd_f32(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, out, 0.0, m, l,
                              heads, scale)
         ctx.pat, ctx.heads, ctx.scale = pat, heads, scale
@@ -129,21 +155,9 @@ class _DotAttnFn(Function):
         dq = torch.empty_like(out)
         ops.dot_attn_bwd_dst_f32(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, m, l, g, c,
                                  dq, Hh, scale)
-        # the source side: the local rows, then the halo rows over the tail of the transposed
-        # row pointer; rows past the pattern's columns have no entries
-        nloc = pat.nsplit if kh is not None else pat.nsplit + pat.H
-        alloc = torch.empty if k.shape[0] == nloc else torch.zeros
-        dk = alloc(k.shape[0], C, dtype=torch.float32, device=g.device)
-        dv = alloc(k.shape[0], C, dtype=torch.float32, device=g.device)
-        ops.dot_attn_bwd_src_f32(pat.t_rowptr[:nloc + 1], pat.t_col, q, g, k, v, m, l, c, dk,
-                                 dv, Hh, scale)
-        dkh = dvh = None
-        if kh is not None:
-            alloc = torch.empty if kh.shape[0] == pat.H else torch.zeros
-            dkh = alloc(kh.shape[0], C, dtype=torch.float32, device=g.device)
-            dvh = alloc(kh.shape[0], C, dtype=torch.float32, device=g.device)
-            ops.dot_attn_bwd_src_f32(pat.t_rowptr[pat.nsplit:], pat.t_col, q, g, kh, vh, m, l,
-                                     c, dkh, dvh, Hh, scale)
+        dk, dv, dkh, dvh = _src_side(pat, k, v, kh, vh, lambda rp, ks, vs, dks, dvs:
+                                     ops.dot_attn_bwd_src_f32(rp, pat.t_col, q, g, ks, vs, m, l,
+                                                              c, dks, dvs, Hh, scale))
         return dq, dk, dv, dkh, dvh, None, None, None
 
 
@@ -158,9 +172,7 @@ class _DotAttnEdgeFn(Function):
         ops = _native.ops()
         q, k, v, kh, vh, edge = (_rows(t) for t in (q, k, v, kh, vh, edge))
         R, C = pat.R, q.shape[1]
-        out = torch.empty(R, C, dtype=torch.float32, device=q.device)
-        m = torch.empty(R, heads, dtype=torch.float32, device=q.device)
-        l = torch.empty_like(m)
+        out, m, l = _out_stats(R, C, heads, q.device)
         ops.dot_attn_edge_fwd_f32(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, edge, out,
                                   0.0, m, l, heads, scale)
         ctx.pat, ctx.heads, ctx.scale = pat, heads, scale
@@ -182,21 +194,9 @@ class _DotAttnEdgeFn(Function):
         w = torch.empty(E, 2 * Hh, dtype=torch.float32, device=g.device)
         ops.dot_attn_edge_bwd_dst_f32(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, edge,
                                       m, l, g, c, dq, dee, w, Hh, scale)
-        # the source side: the local rows, then the halo rows over the tail of the transposed
-        # row pointer; rows past the pattern's columns have no entries
-        nloc = pat.nsplit if kh is not None else pat.nsplit + pat.H
-        alloc = torch.empty if k.shape[0] == nloc else torch.zeros
-        dk = alloc(k.shape[0], C, dtype=torch.float32, device=g.device)
-        dv = alloc(k.shape[0], C, dtype=torch.float32, device=g.device)
-        ops.dot_attn_edge_bwd_src_f32(pat.t_rowptr[:nloc + 1], pat.t_col, pat.t_slot, q, g, w,
-                                      dk, dv, Hh, scale)
-        dkh = dvh = None
-        if kh is not None:
-            alloc = torch.empty if kh.shape[0] == pat.H else torch.zeros
-            dkh = alloc(kh.shape[0], C, dtype=torch.float32, device=g.device)
-            dvh = alloc(kh.shape[0], C, dtype=torch.float32, device=g.device)
-            ops.dot_attn_edge_bwd_src_f32(pat.t_rowptr[pat.nsplit:], pat.t_col, pat.t_slot, q,
-                                          g, w, dkh, dvh, Hh, scale)
+        dk, dv, dkh, dvh = _src_side(pat, k, v, kh, vh, lambda rp, ks, vs, dks, dvs:
+                                     ops.dot_attn_edge_bwd_src_f32(rp, pat.t_col, pat.t_slot, q,
+                                                                   g, w, dks, dvs, Hh, scale))
         return dq, dk, dv, dkh, dvh, dee, None, None, None
 
 
@@ -211,9 +211,7 @@ class _DotAttnDropFn(Function):
         ops = _native.ops()
         q, k, v, kh, vh = (_rows(t) for t in (q, k, v, kh, vh))
         R, C = pat.R, q.shape[1]
-        out = torch.empty(R, C, dtype=torch.float32, device=q.device)
-        m = torch.empty(R, heads, dtype=torch.float32, device=q.device)
-        l = torch.empty_like(m)
+        out, m, l = _out_stats(R, C, heads, q.device)
         ops.dot_attn_drop_fwd_f32(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, out, m, l,
                                   seed, p, heads, scale)
         ctx.pat, ctx.heads, ctx.scale, ctx.p = pat, heads, scale, p
@@ -232,21 +230,10 @@ class _DotAttnDropFn(Function):
         dq = torch.empty_like(out)
         ops.dot_attn_drop_bwd_dst_f32(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, m, l, g,
                                       c, dq, seed, p, Hh, scale)
-        # the source side: the local rows, then the halo rows over the tail of the transposed
-        # row pointer; rows past the pattern's columns have no entries
-        nloc = pat.nsplit if kh is not None else pat.nsplit + pat.H
-        alloc = torch.empty if k.shape[0] == nloc else torch.zeros
-        dk = alloc(k.shape[0], C, dtype=torch.float32, device=g.device)
-        dv = alloc(k.shape[0], C, dtype=torch.float32, device=g.device)
-        ops.dot_attn_drop_bwd_src_f32(pat.t_rowptr[:nloc + 1], pat.t_col, pat.t_slot, q, g, k,
-                                      v, m, l, c, dk, dv, seed, p, Hh, scale)
-        dkh = dvh = None
-        if kh is not None:
-            alloc = torch.empty if kh.shape[0] == pat.H else torch.zeros
-            dkh = alloc(kh.shape[0], C, dtype=torch.float32, device=g.device)
-            dvh = alloc(kh.shape[0], C, dtype=torch.float32, device=g.device)
-            ops.dot_attn_drop_bwd_src_f32(pat.t_rowptr[pat.nsplit:], pat.t_col, pat.t_slot, q,
-                                          g, kh, vh, m, l, c, dkh, dvh, seed, p, Hh, scale)
+        dk, dv, dkh, dvh = _src_side(pat, k, v, kh, vh, lambda rp, ks, vs, dks, dvs:
+                                     ops.dot_attn_drop_bwd_src_f32(rp, pat.t_col, pat.t_slot, q,
+                                                                   g, ks, vs, m, l, c, dks, dvs,
+                                                                   seed, p, Hh, scale))
         return dq, dk, dv, dkh, dvh, None, None, None, None, None
 
 
@@ -373,9 +360,7 @@ class _DotAttnPartsFn(Function):
         qkv = tuple(_rows(t) for t in qkv)
         R, C = pats[0].R, qkv[0].shape[1]
         dev = qkv[0].device
-        out = torch.empty(R, C, dtype=torch.float32, device=dev)
-        m = torch.empty(R, heads, dtype=torch.float32, device=dev)
-        l = torch.empty_like(m)
+        out, m, l = _out_stats(R, C, heads, dev)
         for p, pat in enumerate(pats):
             q, k, v = qkv[3 * p:3 * p + 3]
             if p == 0:
@@ -533,9 +518,7 @@ class _DotAttnHaloFn(Function):
         send = K.gather_rows(kv, plan.send_map.idx)
         recv, work = plan.a2a(send, async_op=True)
         inner, outer = pat.split()
-        out = torch.empty(R, C, dtype=torch.float32, device=q.device)
-        m = torch.empty(R, heads, dtype=torch.float32, device=q.device)
-        l = torch.empty_like(m)
+        out, m, l = _out_stats(R, C, heads, q.device)
         ops.dot_attn_fwd_f32(inner.rowptr, inner.col, q, kv[:, :C], kv[:, C:], None, None,
                              inner.nsplit, out, 0.0, m, l, heads, scale)
         work.wait()

@@ -232,7 +232,7 @@ def test_dot_attn_drop_kernels_wide_operands(C, heads, two):
         _check(f"kernels wide C={C} heads={heads} p={p}", got, C, heads, 0.5, p)
 
 
-# ---------------------------------------------- contract checks (bindings_dot_attn_drop.cpp)
+# --------------------------------------------------- contract checks (bindings_dot_attn.cpp)
 def _valid_args(C, heads):
     rowptr, col, _ = pattern()
     t_rowptr, t_col = transpose(rowptr, col, N)

@@ -259,7 +259,7 @@ def test_dot_attn_edge_kernels_empty_shapes():
         assert torch.equal(dk, torch.zeros_like(dk)) and torch.equal(dv, torch.zeros_like(dv))
 
 
-# ---------------------------------------------- contract checks (bindings_dot_attn_edge.cpp)
+# --------------------------------------------------- contract checks (bindings_dot_attn.cpp)
 def _valid_args(C, heads):
     rowptr, col, _ = pattern()
     t_rowptr, t_col = transpose(rowptr, col, N)
