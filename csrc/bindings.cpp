@@ -292,6 +292,17 @@ void masked_gather_rows_op(const at::Tensor& x, const at::Tensor& idx, const at:
                                   cur_stream(x)));
 }
 
+// sizes only (no read of rowptr from the device): the head count of [E] or [E, H] scores
+int64_t edge_softmax_heads(const at::Tensor& rowptr, const at::Tensor& s) {
+  TORCH_CHECK(rowptr.scalar_type() == at::kLong && rowptr.is_contiguous() &&
+                  rowptr.numel() >= 1,
+              "edge softmax: rowptr must be contiguous int64 with at least one element");
+  TORCH_CHECK(s.dim() == 1 || s.dim() == 2, "edge softmax: scores must be [E] or [E, H]");
+  const int64_t H = s.dim() == 1 ? 1 : s.size(1);
+  TORCH_CHECK(H <= 64, "edge softmax: at most 64 heads, got ", H);
+  return H;
+}
+
 void edge_softmax_fwd_op(const at::Tensor& rowptr, const at::Tensor& s,
                          const at::Tensor& alpha) {
   check_dev(s, s, "scores");
@@ -300,11 +311,12 @@ void edge_softmax_fwd_op(const at::Tensor& rowptr, const at::Tensor& s,
   TORCH_CHECK(s.scalar_type() == at::kFloat && s.is_contiguous() && alpha.is_contiguous() &&
                   alpha.scalar_type() == at::kFloat,
               "edge softmax operands must be contiguous fp32");
-  const int H = s.dim() == 1 ? 1 : static_cast<int>(s.size(1));
+  const int64_t H = edge_softmax_heads(rowptr, s);
+  TORCH_CHECK(alpha.sizes() == s.sizes(), "edge softmax: alpha must have the shape of scores");
   c10::DeviceGuard g(s.device());
   DG_HIP_CHECK(edge_softmax_fwd(rowptr.data_ptr<int64_t>(), s.data_ptr<float>(),
-                                alpha.data_ptr<float>(), rowptr.numel() - 1, H,
-                                cur_stream(s)));
+                                alpha.data_ptr<float>(), rowptr.numel() - 1,
+                                static_cast<int>(H), cur_stream(s)));
 }
 
 void edge_softmax_bwd_op(const at::Tensor& rowptr, const at::Tensor& alpha,
@@ -314,13 +326,16 @@ void edge_softmax_bwd_op(const at::Tensor& rowptr, const at::Tensor& alpha,
   check_dev(grad, alpha, "grad");
   check_dev(ds, alpha, "ds");
   TORCH_CHECK(alpha.is_contiguous() && grad.is_contiguous() && ds.is_contiguous() &&
-                  grad.scalar_type() == at::kFloat,
+                  grad.scalar_type() == at::kFloat && alpha.scalar_type() == at::kFloat &&
+                  ds.scalar_type() == at::kFloat,
               "edge softmax operands must be contiguous fp32");
-  const int H = alpha.dim() == 1 ? 1 : static_cast<int>(alpha.size(1));
+  const int64_t H = edge_softmax_heads(rowptr, alpha);
+  TORCH_CHECK(grad.sizes() == alpha.sizes() && ds.sizes() == alpha.sizes(),
+              "edge softmax: grad and ds must have the shape of alpha");
   c10::DeviceGuard g(alpha.device());
   DG_HIP_CHECK(edge_softmax_bwd(rowptr.data_ptr<int64_t>(), alpha.data_ptr<float>(),
                                 grad.data_ptr<float>(), ds.data_ptr<float>(),
-                                rowptr.numel() - 1, H, cur_stream(alpha)));
+                                rowptr.numel() - 1, static_cast<int>(H), cur_stream(alpha)));
 }
 
 void bias_relu_pack_op(const at::Tensor& y, const c10::optional<at::Tensor>& bias,

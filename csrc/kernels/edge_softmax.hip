@@ -29,6 +29,9 @@ __global__ __launch_bounds__(256) void edge_softmax_fwd_kernel(
       if (hv) m = fmaxf(m, s[j * H + h]);
 #pragma unroll
     for (int off = LPE; off < kWave; off <<= 1) m = fmaxf(m, __shfl_xor(m, off, kWave));
+    // a row whose scores are all -inf: s - m would be NaN; with m = 0 every exp is 0, the
+    // sum is 0 and alpha = 0 (the empty-sum case of `inv` below)
+    if (m == -INFINITY) m = 0.f;
     float sum = 0.f;
     for (int64_t j = b + eg; j < e; j += EPW)
       if (hv) sum += __expf(s[j * H + h] - m);

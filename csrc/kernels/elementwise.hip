@@ -214,7 +214,9 @@ hipError_t col_sum_partial(DType dt, const void* g, int64_t ld, int64_t L, int F
                            float* partial, int nblocks, hipStream_t st) {
   if (L <= 0 || F <= 0) return hipSuccess;
   int vec = dt == DType::F32 ? 4 : 8;
-  if (F % vec != 0 || ld % vec != 0) vec = 1;  // scalar lanes for odd widths (e.g. 73)
+  // scalar lanes for odd widths (e.g. 73) and for a base that is not 16-B aligned (a column
+  // slice starting at a column that is no multiple of vec)
+  if (F % vec != 0 || ld % vec != 0 || reinterpret_cast<uintptr_t>(g) % 16 != 0) vec = 1;
   if (F / vec > 256) return hipErrorInvalidValue;
   const int64_t rpb = (L + nblocks - 1) / nblocks;
   const int tpr = F / vec;

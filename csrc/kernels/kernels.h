@@ -263,7 +263,10 @@ hipError_t masked_gather_rows(DType dt, const void* x, int64_t ldx, const int64_
 // the reference omitted it, RGAT.py:154).
 //   alpha[j, h] = exp(s[j,h] - max_seg) / sum_seg exp(.)
 // backward: ds[j,h] = alpha[j,h] * (g[j,h] - sum_seg alpha*g)
-// Scores are fp32 [E, H] in CSR edge order.
+// Scores are fp32 [E, H] in CSR edge order, H <= 64. A score of -inf gives alpha = 0; a
+// segment whose scores are all -inf gives alpha = 0 for every entry (an empty sum, like an
+// empty segment, which writes nothing). The bindings check that alpha, g and ds have the
+// shape of s; that rowptr describes s is the caller's part.
 // ---------------------------------------------------------------------------
 hipError_t edge_softmax_fwd(const int64_t* rowptr, const float* s, float* alpha,
                             int64_t nrows, int H, hipStream_t stream);
@@ -275,7 +278,9 @@ hipError_t edge_softmax_bwd(const int64_t* rowptr, const float* alpha, const flo
 //   bias_relu_pack: y = act(y + bias) in place; bits (may be null) = keep mask,
 //                   ceil(numel/512)*16 32-bit words (layout: see elementwise.hip).
 //   relu_mask_bwd : g = bit ? g : 0 in place.
-//   col_sum_partial: partial[b, :] = column sums of rows of block b (fp32).
+//   col_sum_partial: partial[b, :] = column sums of rows of block b (fp32); every block
+//                   writes its row, zeros where its row range is empty. 16-B lanes when F
+//                   and ld are multiples of 16 B and g is 16-B aligned, scalar otherwise.
 // ---------------------------------------------------------------------------
 hipError_t bias_relu_pack(DType dt, void* y, const float* bias, uint32_t* bits, int64_t numel,
                           int F, bool relu, hipStream_t stream);
