@@ -244,6 +244,35 @@ hipError_t segment_softmax_edge_bwd(IType it, const int64_t* rowptr, const void*
                                     hipStream_t stream);
 
 // ---------------------------------------------------------------------------
+// Fused gated neighbourhood aggregation (spmm_gated.hip), fp32: the per-channel sigmoid gate
+// of the residual gated graph convolution (PyG's ResGatedGraphConv, GatedGCN). For CSR row r
+// with entries c_k, k indexed by the row, q and v by the column:
+//   z = k[r, f] + q[c_k, f],  s = sigmoid(z)
+//   out[r, f] = sum_k s v[c_k, f]
+//   ds [r, f] = sum_k s (1 - s) v[c_k, f]        (ds null: not computed)
+// ds is the whole saved state of the destination side: dk = g * ds elementwise. Every array
+// has its own base and row stride, unit column stride (q | v are normally the halves of one
+// [N, 2F] buffer, k a column slice of a wider one). An empty row gives exact zeros.
+// accumulate (the halo block after the interior block): out / ds hold an earlier pass's
+// result, which this pass adds to; a row without an entry in this pass is not written.
+// Backward, source side, over the transposed pattern of any subset of the entries (row c =
+// source row of q / v / dq / dv, t_col = destination rows r of k / g):
+//   dv[c, f] = sum_r s g[r, f],   dq[c, f] = v[c, f] sum_r s (1 - s) g[r, f]
+// Every row c < nrows is written (zeros for a source nobody reads). The sigmoid is formed
+// from e = exp(-|z|): finite for every finite z, s (1 - s) = e / (1 + e)^2 exact in both
+// tails. No atomics; fixed summation order, bitwise reproducible.
+// ---------------------------------------------------------------------------
+hipError_t segment_gated_fwd(IType it, const int64_t* rowptr, const void* col, const float* k,
+                             int64_t ldk, const float* q, int64_t ldq, const float* v,
+                             int64_t ldv, float* out, int64_t ldo, float* ds, int64_t ldds,
+                             int64_t nrows, int F, bool accumulate, hipStream_t stream);
+hipError_t segment_gated_bwd_src(IType it, const int64_t* t_rowptr, const void* t_col,
+                                 const float* k, int64_t ldk, const float* q, int64_t ldq,
+                                 const float* v, int64_t ldv, const float* g, int64_t ldg,
+                                 float* dq, int64_t lddq, float* dv, int64_t lddv,
+                                 int64_t nrows, int F, hipStream_t stream);
+
+// ---------------------------------------------------------------------------
 // Row copy with optional source and destination index (K4/K7/K8 replacement, K-new-1).
 //   out[dst(i)] (+)= x[src(i)]   for i in [0, n)
 // src/dst null == identity. src(i) < 0 writes zeros; dst(i) < 0 skips the row.

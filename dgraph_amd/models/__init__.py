@@ -10,6 +10,9 @@ def __getattr__(name):
     if name == "CommAwareGENConv":
         from .genconv import CommAwareGENConv
         return CommAwareGENConv
+    if name == "CommAwareResGatedGraphConv":
+        from .resgated import CommAwareResGatedGraphConv
+        return CommAwareResGatedGraphConv
     if name in ("InnerProductDecoder", "recon_loss", "negative_pattern"):
         from . import link_pred
         return getattr(link_pred, name)

@@ -16,6 +16,9 @@ def __getattr__(name):
     if name == "softmax_aggregate_edge":  # softmax aggregation of per-edge messages
         from .aggregate import softmax_aggregate_edge
         return softmax_aggregate_edge
+    if name == "gated_aggregate":  # per-channel sigmoid-gated neighbourhood sum
+        from .aggregate import gated_aggregate
+        return gated_aggregate
     if name == "gatv2_attention":
         from .gatv2 import gatv2_attention
         return gatv2_attention

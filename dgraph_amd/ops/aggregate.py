@@ -11,6 +11,9 @@
 * :func:`softmax_aggregate_edge` — the same with a per-edge term in the message
   (``relu(x_j + e_ij) + eps``, GENConv with edge features), formed inside the gather pass;
   the backward writes the edge gradient once and sums it once for ``dx``.
+* :func:`gated_aggregate` — the per-channel sigmoid-gated sum (``sum_j sigmoid(k_i + q_j)
+  v_j``, ResGatedGraphConv / GatedGCN) in one gather pass; ``dk`` is an elementwise product
+  with a second output of that pass, ``dq`` / ``dv`` one gather over the transposed pattern.
 * :func:`gather` / :func:`scatter_sum` — vertex->edge gather and edge->vertex scatter-sum
   over a static :class:`~dgraph_amd.ops.csr.IndexMap`; each is the other's adjoint
   (the core contract of the reference, tests/test_NCCLCommPlan.py:100-111,297-307),
@@ -230,6 +233,50 @@ def softmax_aggregate(x: torch.Tensor, csr: CSR, t=1.0) -> torch.Tensor:
     the per-channel gradient). On the GPU (fp32) one kernel gathers each neighbour row once
     and writes nothing per edge, and one kernel computes ``dx`` and ``dt``."""
     return _SoftmaxAggregateFn.apply(vec_rows(x), as_temperature(t, x), csr)
+
+
+class _GatedAggregateFn(Function):
+    """Gated aggregation (K.segment_gated). The forward keeps ``ds = sum_j s (1 - s) v_j``
+    from the same pass, which is the whole destination side of the backward (``dk = g *
+    ds``); the source side recomputes every gate in one gather over the transposed pattern,
+    which gives ``dq`` and ``dv`` together."""
+
+    @staticmethod
+    def forward(ctx, k, q, v, csr: CSR):
+        out, ds = K.segment_gated(csr.rowptr, csr.col, k, q, v,
+                                  want_ds=ctx.needs_input_grad[0])
+        ctx.csr = csr
+        ctx.save_for_backward(k, q, v, ds)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        k, q, v, ds = ctx.saved_tensors
+        g = vec_rows(g)
+        dk = g * ds if ctx.needs_input_grad[0] else None
+        dq = dv = None
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            tr = ctx.csr.transpose()
+            dq, dv = K.segment_gated_bwd_src(tr.rowptr, tr.col, k, q, v, g)
+        return dk, dq, dv, None
+
+
+def gated_aggregate(k: torch.Tensor, q: torch.Tensor, v: torch.Tensor, csr: CSR) -> torch.Tensor:
+    """Gated aggregation (the neighbourhood sum of PyG's ``ResGatedGraphConv`` and of
+    GatedGCN): ``out[r, f] = sum_j sigmoid(k[r, f] + q[j, f]) v[j, f]`` over the entries ``j``
+    of row ``r`` (0 for an empty row), a sigmoid gate per channel. ``k``: ``[csr.num_rows,
+    F]``; ``q``, ``v``: ``[csr.num_cols, F]``; each may be a column view of a wider buffer
+    (the ``[k | q | v]`` of one projection). On the GPU (fp32) one kernel gathers each
+    neighbour's ``q`` and ``v`` rows once and writes nothing per edge; ``dk`` is an
+    elementwise product with a second output of that pass, and one kernel over the transposed
+    pattern computes ``dq`` and ``dv``."""
+    if k.dim() != 2 or q.shape != v.shape or q.dim() != 2 or q.shape[1] != k.shape[1]:
+        raise ValueError(f"gated_aggregate: k [R, F], q and v [C, F] expected, got "
+                         f"{tuple(k.shape)}, {tuple(q.shape)}, {tuple(v.shape)}")
+    if k.shape[0] != csr.num_rows or q.shape[0] != csr.num_cols:
+        raise ValueError(f"gated_aggregate: k needs {csr.num_rows} rows and q / v "
+                         f"{csr.num_cols}, got {k.shape[0]} and {q.shape[0]}")
+    return _GatedAggregateFn.apply(vec_rows(k), vec_rows(q), vec_rows(v), csr)
 
 
 @dataclass

@@ -509,6 +509,100 @@ def segment_softmax_bwd(
     return dx, part
 
 
+def _check_gated_rows(name: str, F: int, ref: torch.Tensor, **arrays) -> None:
+    """The operands of the gated aggregation: 2-D, ``F`` wide, of ``ref``'s dtype (fp32 on
+    the GPU) on its device, unit column stride."""
+    if ref.is_cuda and ref.dtype != torch.float32:
+        raise ValueError(f"{name}: the GPU kernels are float32, got {ref.dtype}")
+    for nm, a in arrays.items():
+        if a is None:
+            continue
+        if a.dim() != 2 or a.shape[1] != F:
+            raise ValueError(f"{name}: {nm} must be [rows, {F}], got {tuple(a.shape)}")
+        if a.dtype != ref.dtype or a.device != ref.device:
+            raise ValueError(f"{name}: {nm} must be {ref.dtype} on {ref.device}, got "
+                             f"{a.dtype} on {a.device}")
+        if F > 1 and a.shape[0] > 0 and a.stride(1) != 1:
+            raise ValueError(f"{name}: {nm} must have unit column stride, got strides "
+                             f"{a.stride()}")
+
+
+def segment_gated(
+    rowptr: torch.Tensor,
+    col: torch.Tensor,
+    k: torch.Tensor,
+    q: torch.Tensor,
+    v: torch.Tensor,
+    out: Optional[torch.Tensor] = None,
+    ds: Optional[torch.Tensor] = None,
+    *,
+    want_ds: bool = False,
+    accumulate: bool = False,
+):
+    """Gated aggregation of each CSR row's entries in ONE pass over the neighbour rows: with
+    ``s = sigmoid(k[r, f] + q[col[j], f])``, ``out[r, f] = sum_j s v[col[j], f]`` and, with
+    ``want_ds`` or a ``ds`` buffer, ``ds[r, f] = sum_j s (1 - s) v[col[j], f]`` from the same
+    pass (zeros for an empty row). ``ds`` is the whole saved state of the destination side:
+    ``dk = g * ds``. ``k`` has the CSR's rows, ``q`` / ``v`` the rows its column ids index;
+    every operand may be a column view of a wider buffer (its own row stride).
+
+    ``accumulate``: ``out`` (and ``ds``) hold the result of an earlier pass over another
+    source (the interior block), which this pass adds to; a row without an entry here is left
+    bitwise as it is. Returns ``(out, ds)`` (``ds`` is ``None`` when not asked for)."""
+    R = rowptr.numel() - 1
+    F = k.shape[1]
+    if accumulate and (out is None or (want_ds and ds is None)):
+        raise ValueError("segment_gated: accumulate needs explicit out (and ds with want_ds)")
+    if out is None:
+        out = torch.empty(R, F, dtype=k.dtype, device=k.device)
+    if ds is None and want_ds:
+        ds = torch.empty(out.shape[0], F, dtype=k.dtype, device=k.device)
+    _check_gated_rows("segment_gated", F, k, k=k, q=q, v=v, out=out, ds=ds)
+    if q.shape[0] != v.shape[0]:
+        raise ValueError("segment_gated: q and v must have the same row count, got "
+                         f"{q.shape[0]} and {v.shape[0]}")
+    if k.shape[0] < R or out.shape[0] < R or (ds is not None and ds.shape[0] < R):
+        raise ValueError(f"segment_gated: k, out and ds need >= {R} rows")
+    if _native_ok(k):
+        _native.ops().segment_gated_fwd(rowptr, col, k, q, v, out, ds, bool(accumulate))
+        return out, ds
+    return _ref.segment_gated(rowptr, col, k, q, v, out, ds, accumulate)
+
+
+def segment_gated_bwd_src(
+    t_rowptr: torch.Tensor,
+    t_col: torch.Tensor,
+    k: torch.Tensor,
+    q: torch.Tensor,
+    v: torch.Tensor,
+    g: torch.Tensor,
+    dq: Optional[torch.Tensor] = None,
+    dv: Optional[torch.Tensor] = None,
+):
+    """Source side of the backward of :func:`segment_gated` as a gather over the transposed
+    pattern (``t_rowptr`` / ``t_col``: rows = source rows of ``q`` / ``v``, columns =
+    destination rows of ``k`` / ``g``) of ANY subset of the entries: per entry ``s =
+    sigmoid(k[r] + q[c])``, ``dv[c] = sum s g[r]`` and ``dq[c] = v[c] sum s (1 - s) g[r]``.
+    Every source row is written (zeros for one nobody reads). ``dq`` / ``dv`` may be the
+    halves of one ``[C, 2F]`` buffer. No atomics. Returns ``(dq, dv)``."""
+    C = t_rowptr.numel() - 1
+    F = q.shape[1]
+    if dq is None:
+        dq = torch.empty(C, F, dtype=q.dtype, device=q.device)
+    if dv is None:
+        dv = torch.empty(C, F, dtype=q.dtype, device=q.device)
+    _check_gated_rows("segment_gated_bwd_src", F, q, k=k, q=q, v=v, g=g, dq=dq, dv=dv)
+    if min(q.shape[0], v.shape[0], dq.shape[0], dv.shape[0]) < C:
+        raise ValueError(f"segment_gated_bwd_src: q, v, dq and dv need >= {C} rows")
+    if k.shape[0] < g.shape[0]:
+        raise ValueError("segment_gated_bwd_src: k has fewer rows than g "
+                         f"({k.shape[0]} < {g.shape[0]})")
+    if _native_ok(q):
+        _native.ops().segment_gated_bwd_src(t_rowptr, t_col, k, q, v, g, dq, dv)
+        return dq, dv
+    return _ref.segment_gated_bwd_src(t_rowptr, t_col, k, q, v, g, dq, dv)
+
+
 def _check_edge_rows(name: str, x: torch.Tensor, e: torch.Tensor, col: torch.Tensor) -> None:
     """The edge rows of :func:`segment_softmax_edge`: ``[nnz, F]`` of ``x``'s dtype (fp32 on
     the GPU) on its device, unit column stride."""

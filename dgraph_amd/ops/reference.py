@@ -335,6 +335,60 @@ def segment_softmax_bwd(t_rowptr, t_col, x, t, g, out_fwd, lse, dx, want_dt=True
     return dx, part
 
 
+def _gate(z):
+    """``(s, s (1 - s))`` of ``s = sigmoid(z)`` from ``e = exp(-|z|)``, as the kernel forms
+    them: finite for every finite ``z``, the derivative accurate in both tails."""
+    e = torch.exp(-z.abs())
+    r = 1.0 / (1.0 + e)
+    return torch.where(z >= 0, r, e * r), e * r * r
+
+
+def segment_gated(rowptr, col, k, q, v, out, ds=None, accumulate=False):
+    """Gated aggregation of each CSR row's entries (cf. kernels.h): with ``s = sigmoid(k[r] +
+    q[col[j]])``, ``out[r] = sum_j s v[col[j]]`` and, when ``ds`` is given, ``ds[r] = sum_j
+    s (1 - s) v[col[j]]``; zeros for an empty row. ``accumulate``: ``out`` / ``ds`` hold an
+    earlier pass's result, which this pass adds to; a row without an entry here keeps it
+    bitwise. fp32 (fp64 for fp64 input)."""
+    R = rowptr.numel() - 1
+    F = k.shape[1]
+    if R <= 0 or F == 0:
+        return out, ds
+    cdt = torch.float64 if k.dtype == torch.float64 else torch.float32
+    rows = _row_ids(rowptr)
+    c = col.long()
+    s, d = _gate(k.to(cdt)[:R][rows] + q.to(cdt)[c])
+    vv = v.to(cdt)[c]
+    visited = ((rowptr[1:] - rowptr[:-1]) > 0).unsqueeze(1)
+    for dst, w in ((out, s), (ds, d)):
+        if dst is None:
+            continue
+        acc = torch.zeros(R, F, dtype=cdt, device=k.device).index_add_(0, rows, w * vv)
+        if accumulate:
+            acc = torch.where(visited, dst[:R].to(cdt) + acc, dst[:R].to(cdt))
+        dst[:R] = acc.to(dst.dtype)
+    return out, ds
+
+
+def segment_gated_bwd_src(t_rowptr, t_col, k, q, v, g, dq, dv):
+    """Source side of the backward of :func:`segment_gated` over the transposed pattern of
+    any subset of the entries (cf. kernels.h): per entry ``r = t_col[j]`` of source row ``c``,
+    ``s = sigmoid(k[r] + q[c])``; ``dv[c] = sum s g[r]`` and ``dq[c] = v[c] sum s (1 - s)
+    g[r]``. Every row ``c`` is written. Returns ``(dq, dv)``."""
+    C = t_rowptr.numel() - 1
+    F = dq.shape[1]
+    if C <= 0 or F == 0:
+        return dq, dv
+    cdt = torch.float64 if dq.dtype == torch.float64 else torch.float32
+    src = _row_ids(t_rowptr)
+    r = t_col.long()
+    s, d = _gate(k.to(cdt)[r] + q.to(cdt)[:C][src])
+    gg = g.to(cdt)[r]
+    zero = lambda: torch.zeros(C, F, dtype=cdt, device=dq.device)  # noqa: E731
+    dv[:C] = zero().index_add_(0, src, s * gg).to(dv.dtype)
+    dq[:C] = (v.to(cdt)[:C] * zero().index_add_(0, src, d * gg)).to(dq.dtype)
+    return dq, dv
+
+
 def _edge_message(x, e, col, relu, eps, cdt):
     """``(z, m)`` per CSR slot: ``z = x[col] + e`` and ``m = (relu ? max(z, 0) : z) + eps``."""
     z = x.to(cdt)[col.long()] + e.to(cdt)

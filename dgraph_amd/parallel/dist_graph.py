@@ -762,6 +762,108 @@ class DistGraph:
             K.spmm(st.rowptr, st.col, sg, oc, beta=1.0, split=_hs(st), row_map=st.row_map)
         return dx, dt
 
+    def aggregate_gated(self, k: torch.Tensor, qv: torch.Tensor,
+                        halo_rows: Optional[torch.Tensor] = None):
+        """Gated aggregation over in-neighbours, local and halo (``out[r, f] = sum_j
+        sigmoid(k[r, f] + q[j, f]) v[j, f]``, :func:`~dgraph_amd.ops.kernels.segment_gated`),
+        on the schedule of :meth:`aggregate_softmax`. ``k``: ``[L, F]``; ``qv``: the local
+        ``[L, 2F]`` source buffer ``[q | v]``, whose ``send_map`` rows go on the links as ONE
+        message while the interior pass runs; the halo block is then added over all ``L``
+        rows. Returns ``(out, saved)``; ``saved`` is what :meth:`aggregate_gated_T` needs
+        (``ds``, the destination-side state ``sum_j s (1 - s) v_j``, and ``halo``, the ``[H,
+        2F]`` halo rows this pass read). ``halo_rows`` as in :meth:`aggregate`."""
+        self.edges_aggregated += self.nnz
+        L, F = self.L, k.shape[1]
+        if qv.dim() != 2 or qv.shape[1] != 2 * F:
+            raise ValueError(f"aggregate_gated: qv must be [L, {2 * F}] ([q | v]), got "
+                             f"{tuple(qv.shape)}")
+        it = self.interior
+        out = torch.empty(L, F, dtype=k.dtype, device=k.device)
+        ds = torch.empty(L, F, dtype=k.dtype, device=k.device)
+        saved = dict(ds=ds, halo=None)
+        if self.halo is None or halo_rows is not None:
+            K.segment_gated(it.rowptr, it.col, k, qv[:, :F], qv[:, F:], out, ds)
+            if self.halo is not None:
+                K.segment_gated(self.halo.rowptr, self.halo.col, k, halo_rows[:, :F],
+                                halo_rows[:, F:], out, ds, accumulate=True)
+            saved["halo"] = halo_rows
+            return out, saved
+        # the exchanges depend on the plan alone (a rank with sends and no halo entry posts
+        # them too); a column chunk carries the same channel range of q and of v
+        idx = self.send_map.idx
+        pend = []
+        for c0, c1 in self._col_chunks(self.a2a, F, 2 * k.element_size()):
+            if (c0, c1) == (0, F):
+                send = K.gather_rows(qv, idx)
+            else:
+                w = c1 - c0
+                send = torch.empty(idx.numel(), 2 * w, dtype=qv.dtype, device=qv.device)
+                K.copy_rows(qv[:, c0:c1], src_idx=idx, out=send[:, :w])
+                K.copy_rows(qv[:, F + c0:F + c1], src_idx=idx, out=send[:, w:])
+            recv, work = self.a2a(send, async_op=True)
+            if not self.overlap:
+                work.wait()
+            pend.append((c0, c1, recv, work))
+        K.segment_gated(it.rowptr, it.col, k, qv[:, :F], qv[:, F:], out, ds)
+        for c0, c1, recv, work in pend:
+            work.wait()
+            whole, w = (c0, c1) == (0, F), c1 - c0
+            K.segment_gated(self.halo.rowptr, self.halo.col, k if whole else k[:, c0:c1],
+                            recv[:, :w], recv[:, w:], out if whole else out[:, c0:c1],
+                            ds if whole else ds[:, c0:c1], accumulate=True)
+        if len(pend) == 1:
+            saved["halo"] = pend[0][2]
+        else:  # back to [q | v]
+            saved["halo"] = torch.cat([p[2][:, :p[1] - p[0]] for p in pend] +
+                                      [p[2][:, p[1] - p[0]:] for p in pend], 1)
+        return out, saved
+
+    def aggregate_gated_T(self, g: torch.Tensor, k: torch.Tensor, qv: torch.Tensor,
+                          saved: dict):
+        """Backward of :meth:`aggregate_gated` (``g``: ``[L, F]``; ``k``, ``qv`` and
+        ``saved``: the forward's inputs and second result). The destination side is ``dk = g
+        * ds``, no kernel. The source side recomputes every gate: the interior entries over
+        the interior's transposed pattern with the local ``[q | v]`` into ``d[q | v]``, the
+        halo block's over its transposed pattern with the kept halo rows into ``[H, 2F]``
+        rows, which then take the reverse path of :meth:`aggregate_softmax_T` as one message
+        (reverse exchange under the interior pass, owner-side segment sum). Returns ``(dk,
+        dqv)``."""
+        g = vec_rows(g)
+        L, F = self.L, k.shape[1]
+        it = self.interior if self.interior.symmetric else self.interior.transpose()
+        self.edges_aggregated += it.nnz + (self.halo.nnz if self.halo is not None else 0)
+        dk = g * saved["ds"]
+        dqv = torch.empty(L, 2 * F, dtype=k.dtype, device=k.device)
+        q, v, dq, dv = qv[:, :F], qv[:, F:], dqv[:, :F], dqv[:, F:]
+        if self.halo is None:
+            K.segment_gated_bwd_src(it.rowptr, it.col, k, q, v, g, dq, dv)
+            return dk, dqv
+        ht = self.halo.transpose()
+        qvh = saved["halo"]
+        pend = []
+        for c0, c1 in self._col_chunks(self.a2a_rev, F, 2 * g.element_size()):
+            whole, w = (c0, c1) == (0, F), c1 - c0
+            cut = (lambda t: t) if whole else (lambda t: t[:, c0:c1])  # noqa: E731
+            hg = torch.empty(ht.num_rows, 2 * w, dtype=k.dtype, device=k.device)
+            K.segment_gated_bwd_src(ht.rowptr, ht.col, cut(k), qvh[:, c0:c1],
+                                    qvh[:, F + c0:F + c1], cut(g), hg[:, :w], hg[:, w:])
+            sg, work = self.a2a_rev(hg, async_op=True)
+            if not self.overlap:
+                work.wait()
+            pend.append((c0, c1, sg, work))
+        K.segment_gated_bwd_src(it.rowptr, it.col, k, q, v, g, dq, dv)
+        st = self.send_map.transpose_csr().compact_rows()
+        for c0, c1, sg, work in pend:
+            work.wait()
+            if (c0, c1) == (0, F):  # the message has the layout of dqv
+                K.spmm(st.rowptr, st.col, sg, dqv, beta=1.0, split=_hs(st), row_map=st.row_map)
+                continue
+            w = c1 - c0
+            for src, dst in ((sg[:, :w], dq[:, c0:c1]), (sg[:, w:], dv[:, c0:c1])):
+                K.spmm(st.rowptr, st.col, src, dst, beta=1.0, split=_hs(st),
+                       row_map=st.row_map)
+        return dk, dqv
+
     def _edge_blocks(self, e_int, e_halo, x: torch.Tensor, name: str):
         """The per-slot edge rows of the two blocks, checked: ``e_int`` ``[interior.nnz, F]``
         and ``e_halo`` ``[halo.nnz, F]`` (``None`` where the block has no entry)."""
@@ -1287,6 +1389,35 @@ def dist_softmax_aggregate(x: torch.Tensor, graph: DistGraph, t=1.0) -> torch.Te
     :meth:`DistGraph.aggregate_softmax`). ``t`` as there; its gradient is this rank's part
     (``t`` is a replicated parameter: all-reduce it with the other weight gradients)."""
     return _DistSoftmaxAggregateFn.apply(x, as_temperature(t, x), graph)
+
+
+class _DistGatedAggregateFn(Function):
+    @staticmethod
+    def forward(ctx, k, qv, graph: DistGraph):
+        k, qv = vec_rows(k), vec_rows(qv)
+        out, saved = graph.aggregate_gated(k, qv)
+        ctx.graph = graph
+        ctx.save_for_backward(k, qv, saved["ds"], saved["halo"])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        k, qv, ds, halo = ctx.saved_tensors
+        dk, dqv = ctx.graph.aggregate_gated_T(g, k, qv, dict(ds=ds, halo=halo))
+        return dk, dqv, None
+
+
+def dist_gated_aggregate(k: torch.Tensor, qv: torch.Tensor, graph: DistGraph) -> torch.Tensor:
+    """Autograd-aware distributed :func:`~dgraph_amd.ops.aggregate.gated_aggregate` over
+    every local vertex's in-neighbours, local and halo: ``out[i] = sum_j sigmoid(k[i] + q[j])
+    v[j]`` per channel, with ``k`` ``[L, F]`` and ``qv`` the local ``[L, 2F]`` buffer ``[q |
+    v]`` (one exchange of ``[q | v]`` rows forward, one of ``d[q | v]`` rows backward;
+    :meth:`DistGraph.aggregate_gated`). Both may be column views of one projection."""
+    if k.dim() != 2 or qv.dim() != 2 or qv.shape[1] != 2 * k.shape[1] or \
+            k.shape[0] != qv.shape[0]:
+        raise ValueError(f"dist_gated_aggregate: k [L, F] and qv [L, 2F] expected, got "
+                         f"{tuple(k.shape)} and {tuple(qv.shape)}")
+    return _DistGatedAggregateFn.apply(k, qv, graph)
 
 
 class _DistSoftmaxAggregateEdgeFn(Function):
