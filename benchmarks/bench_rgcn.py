@@ -58,7 +58,8 @@ def parse(argv=None):
     ap.add_argument("--dtype", choices=("fp32", "bf16"), default="fp32",
                     help="compute/storage dtype (fp32 = the reference's precision: "
                          "experiments/OGB-LSC/RGAT.py has no casts; bf16 = autocast with fp32 "
-                         "master weights, a secondary)")
+                         "master weights, a secondary; --model rgat: bf16 features and rows "
+                         "on the lean path, fp32 parameters, no autocast)")
     ap.add_argument("--path", choices=("auto", "lean", "aggregate-first"), default="auto",
                     help="R-GCN execution path (auto: lean at fp32, aggregate-first under bf16)")
     ap.add_argument("--link-gbps", type=float, default=0.0,
@@ -68,7 +69,7 @@ def parse(argv=None):
                          "exposes")
     ap.add_argument("--model", choices=("rgcn", "rgat"), default="rgcn",
                     help="rgat: the reference's OGB-LSC model (experiments/OGB-LSC/RGAT.py) on "
-                         "its lean fp32 path (fused relation attention, ops/gat.py)")
+                         "its lean path (fused relation attention, ops/gat.py; fp32 or bf16 rows)")
     ap.add_argument("--heads", type=int, default=4,
                     help="RGAT attention heads (the reference config's 4)")
     ap.add_argument("--verbose", action="store_true")
@@ -159,8 +160,6 @@ def main(argv=None):
     if args.model == "rgat":
         from dgraph_amd.models.rgat import CommAwareRGAT
 
-        if dtype != torch.float32:
-            raise SystemExit("[bench_rgcn] --model rgat runs the lean fp32 path only")
         model = CommAwareRGAT(shape.num_features, shape.num_classes, args.hidden,
                               len(EDGE_TYPES), args.layers, args.heads, comm=comm,
                               dropout=args.dropout, bn_group=comm.group).to(dev)
@@ -173,7 +172,9 @@ def main(argv=None):
     opt = torch.optim.Adam(model.parameters(), lr=args.lr, fused=dev.type == "cuda")
     sync = GradSync(model.parameters(), group=comm.group) if world > 1 else None
     inv_n = 1.0 / max(n_train, 1)
-    use_amp = dev.type == "cuda" and dtype == torch.bfloat16
+    # (RGAT at bf16: bf16 features on the lean path, fp32 parameters; its custom functions
+    # take the rows' dtype, no autocast)
+    use_amp = dev.type == "cuda" and dtype == torch.bfloat16 and args.model != "rgat"
 
     lean = True if args.model == "rgat" else (
         model.lean if model.lean is not None else (dtype == torch.float32))

@@ -1,6 +1,6 @@
 // dgraph_amd — argument checkers shared by the bindings of the fused fp32 attention kernels
-// (bindings_gat.cpp, bindings_gatv2.cpp, bindings_dot_attn.cpp). `op` is the op family's
-// name, the prefix of every message ("gatv2", "dot_attn_edge", ...).
+// (bindings_gat.cpp, bindings_gat_bf16.cpp, bindings_gatv2.cpp, bindings_dot_attn.cpp). `op`
+// is the op family's name, the prefix of every message ("gatv2", "dot_attn_edge", ...).
 #pragma once
 
 #include <ATen/ATen.h>
@@ -34,6 +34,27 @@ inline void rows_f32(const char* op, const at::Tensor& t, const at::Tensor& ref,
                   al16(t.data_ptr()),
               op, ": ", name, " must have unit column stride, a row stride divisible by 4 "
               "and 16-B alignment, got strides ", t.strides());
+}
+
+// a bf16 feature array: [>= min_rows, C] bfloat16, unit column stride, 16-B aligned rows
+// (eight channels per 16-B vector)
+inline void rows_bf16(const char* op, const at::Tensor& t, const at::Tensor& ref,
+                      int64_t min_rows, int64_t cols, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == ref.device(), op, ": ", name, " must be on ",
+              ref.device());
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16 && t.dim() == 2 && t.size(1) == cols &&
+                  t.size(0) >= min_rows,
+              op, ": ", name, " must be bfloat16 [>= ", min_rows, ", ", cols, "], got ",
+              t.scalar_type(), " ", t.sizes());
+  if (t.size(0) == 0) return;
+  TORCH_CHECK(t.stride(1) == 1 && t.stride(0) % 8 == 0 && t.stride(0) >= cols &&
+                  al16(t.data_ptr()),
+              op, ": ", name, " must have unit column stride, a row stride divisible by 8 "
+              "and 16-B alignment, got strides ", t.strides());
+}
+
+inline const uint16_t* bf16_ptr(const at::Tensor& t) {
+  return reinterpret_cast<const uint16_t*>(t.data_ptr());
 }
 
 // per-head arrays: [>= min_rows, heads] with unit column stride and the shared row stride

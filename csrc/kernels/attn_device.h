@@ -1,7 +1,9 @@
 // dgraph_amd — device helpers shared by the row-parallel fp32 attention kernels
 // (gat_f32.hip, gatv2_f32.hip, dot_attn_f32.h). All of them lay a row out the same way: one
 // group of LPR = C / 4 lanes per row (16-B fp32 vectors), kWave / LPR row groups per wave,
-// the heads as contiguous blocks of LH = LPR / heads lanes.
+// the heads as contiguous blocks of LH = LPR / heads lanes. gat_bf16.hip keeps the layout
+// with eight bf16 channels per lane (LPR = C / 8): its unpack / pack and 8-term helpers are
+// at the end.
 #pragma once
 
 #include "../common.h"
@@ -55,6 +57,64 @@ __device__ __forceinline__ float4 add4(const float4& a, const float4& b) {
 
 __device__ __forceinline__ const float4* vec(const float* p) {
   return reinterpret_cast<const float4*>(p);
+}
+
+// ---- bf16 storage (gat_bf16.hip): a lane's eight channels are one 16-B vector of bf16,
+// widened to fp32 by a 16-bit shift (exact) and narrowed once, at the store, by
+// round-to-nearest-even (Inf and NaN pass through). LPR = C / 8 there.
+struct f32x8 {
+  float4 lo, hi;
+};
+
+__device__ __forceinline__ f32x8 zero8() {
+  f32x8 v;
+  v.lo = make_float4(0.f, 0.f, 0.f, 0.f);
+  v.hi = make_float4(0.f, 0.f, 0.f, 0.f);
+  return v;
+}
+
+__device__ __forceinline__ f32x8 unpack_bf16x8(const uint4& r) {
+  f32x8 v;
+  v.lo.x = __uint_as_float(r.x << 16);
+  v.lo.y = __uint_as_float(r.x & 0xffff0000u);
+  v.lo.z = __uint_as_float(r.y << 16);
+  v.lo.w = __uint_as_float(r.y & 0xffff0000u);
+  v.hi.x = __uint_as_float(r.z << 16);
+  v.hi.y = __uint_as_float(r.z & 0xffff0000u);
+  v.hi.z = __uint_as_float(r.w << 16);
+  v.hi.w = __uint_as_float(r.w & 0xffff0000u);
+  return v;
+}
+
+__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
+  return static_cast<uint32_t>(f32_to_bf16(a)) | (static_cast<uint32_t>(f32_to_bf16(b)) << 16);
+}
+
+__device__ __forceinline__ uint4 pack_bf16x8(const f32x8& v) {
+  return make_uint4(pack_bf16x2(v.lo.x, v.lo.y), pack_bf16x2(v.lo.z, v.lo.w),
+                    pack_bf16x2(v.hi.x, v.hi.y), pack_bf16x2(v.hi.z, v.hi.w));
+}
+
+// this lane's eight terms of <a, b>, one fixed order (see dot4)
+__device__ __forceinline__ float dot8(const f32x8& a, const f32x8& b) {
+  float p = a.lo.x * b.lo.x;
+  p = fmaf(a.lo.y, b.lo.y, p);
+  p = fmaf(a.lo.z, b.lo.z, p);
+  p = fmaf(a.lo.w, b.lo.w, p);
+  p = fmaf(a.hi.x, b.hi.x, p);
+  p = fmaf(a.hi.y, b.hi.y, p);
+  p = fmaf(a.hi.z, b.hi.z, p);
+  return fmaf(a.hi.w, b.hi.w, p);
+}
+
+__device__ __forceinline__ void axpy8(float w, const f32x8& x, f32x8& acc) {
+  axpy4(w, x.lo, acc.lo);
+  axpy4(w, x.hi, acc.hi);
+}
+
+__device__ __forceinline__ void scale8(float w, f32x8& acc) {
+  acc.lo = make_float4(acc.lo.x * w, acc.lo.y * w, acc.lo.z * w, acc.lo.w * w);
+  acc.hi = make_float4(acc.hi.x * w, acc.hi.y * w, acc.hi.z * w, acc.hi.w * w);
 }
 
 }  // namespace dgraph

@@ -510,6 +510,48 @@ hipError_t gat_bwd_src_f32(IType it, const int64_t* rowptr, const void* col, int
                            hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// The same relation attention with bf16 storage (gat_bf16.hip). Per head k of C = heads D:
+//   ss_j  = <z_j[kD:(k+1)D], a_src[k]>     computed in the kernel from the gathered bf16 row
+//   e_ij  = leaky_relu(sd_i[k] + ss_j, slope);  alpha = softmax_j(e_ij) over the row's entries
+//   out_i = bf16_rne(beta out_i + sum_j alpha_ij z_j[head k])
+// There is no ss operand: all three kernels compute ss with one function in one order, so
+// the backward kernels recompute the forward's scores bit for bit.
+// * bf16 (raw uint16): z, zh (second source: columns >= nsplit; nullable), out, g = dL/dout,
+//   gz. Every one has its own row stride in ELEMENTS (a multiple of 8; rows 16-B aligned), so
+//   z may be a column view of a wider GEMM output.
+// * fp32: sd, stat_m, stat_l (= 1 / sum, 0 for an empty row), c, gsd, gss — contiguous
+//   [rows, heads] — a_src ([C], 16-B aligned) and da_part. All arithmetic is fp32; a bf16
+//   value is widened by a 16-bit shift and narrowed once, at the store, by
+//   round-to-nearest-even (Inf / NaN pass through).
+// * col is int32. (C, heads): C in 64 / 128 / 256, heads in 1 / 2 / 4 / 8 (gat_bf16_shape_ok).
+// * An empty row writes beta out, stat_l = 0 (stat_m = -inf) and zeros for its gradients.
+// * A launch needs row 0 of the first gathered source (bwd_src: of g, sd, m_dst, l_dst,
+//   c_dst) to exist: padding slots read it with weight 0.
+// * gat_bwd_src_bf16 (rows = source rows with z resident, col = destination ids) also writes
+//   da_part [P, C], P = gat_bf16_da_parts(nrows, C) (a function of (nrows, C) only; every row
+//   is written): sum_p da_part[p, kD + d] = sum_j gss_j[k] z_j[kD + d] = dL/da_src[k, d].
+// No atomics, no LDS, no scratch, fixed summation orders: two calls give equal bits.
+bool gat_bf16_shape_ok(int C, int heads);
+int64_t gat_bf16_da_parts(int64_t nrows, int C);
+hipError_t gat_fwd_bf16(const int64_t* rowptr, const int32_t* col, int64_t nrows, int C,
+                        int heads, float slope, const uint16_t* z, int64_t ldz,
+                        const uint16_t* zh, int64_t ldzh, int64_t nsplit, const float* a_src,
+                        const float* sd, uint16_t* out, int64_t ldo, float beta, float* stat_m,
+                        float* stat_l, hipStream_t st);
+hipError_t gat_bwd_dst_bf16(const int64_t* rowptr, const int32_t* col, int64_t nrows, int C,
+                            int heads, float slope, const uint16_t* z, int64_t ldz,
+                            const uint16_t* zh, int64_t ldzh, int64_t nsplit,
+                            const float* a_src, const float* sd, const float* stat_m,
+                            const float* stat_l, const uint16_t* g, int64_t ldg, float* c_out,
+                            float* gsd_out, hipStream_t st);
+hipError_t gat_bwd_src_bf16(const int64_t* rowptr, const int32_t* col, int64_t nrows, int C,
+                            int heads, float slope, const uint16_t* g, int64_t ldg,
+                            const uint16_t* z, int64_t ldz, const float* a_src,
+                            const float* sd, const float* m_dst, const float* l_dst,
+                            const float* c_dst, uint16_t* gz, int64_t ldgz, float* gss,
+                            float* da_part, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // Fused fp32 scaled dot-product graph attention of one relation (dot_attn_f32.h):
 // e_ij = scale <q_i, k_j> per head, softmax over each destination row's edges, the weighted
 // gather of v_j, and the exact adjoint (destination side: dq; source side over the

@@ -38,6 +38,14 @@ def _torch_dirs():
     return inc, root / "lib"
 
 
+# per-file flags, by file name: gat_bf16.hip is built without the packed-fp32 VALU forms
+# (its 8-channel axpys are what the compiler would pair up; plain fp32 fmas keep every lane's
+# operation order the one written down)
+EXTRA_FLAGS = {
+    "gat_bf16.hip": ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"],
+}
+
+
 def _hipcc() -> str:
     for cand in (ROCM / "bin" / "hipcc", shutil.which("hipcc")):
         if cand and Path(cand).exists():
@@ -87,7 +95,7 @@ def _compile(src: Path, force: bool, newest_header: float) -> Path:
     ):
         return obj
     obj.parent.mkdir(parents=True, exist_ok=True)
-    cmd = [_hipcc()] + _common_flags()
+    cmd = [_hipcc()] + _common_flags() + EXTRA_FLAGS.get(src.name, [])
     if src.suffix == ".hip":
         cmd += [f"--offload-arch={ARCH}", "-x", "hip", "-c", str(src), "-o", str(obj)]
     else:

@@ -32,7 +32,10 @@ relation's ``W_r``, and each relation's destination-score projection
 kernel of ``ops/gat.py`` added in place into its destination's pre-activation, with its halo
 rows exchanged by one all-to-all-v (layer 0: the kept halo feature rows are transformed
 locally, no exchange) and read as a second source (no ``torch.cat``); BN / ReLU / dropout are
-recomputed in backward instead of stored.
+recomputed in backward instead of stored. With bf16 features (fp32 parameters) the same path
+runs on bf16 rows: the dense side on what ``act_linears`` does for bf16 (the library GEMM),
+the attention on the bf16-storage kernels (csrc/kernels/gat_bf16.hip), the destination scores
+in fp32.
 """
 from __future__ import annotations
 
@@ -356,7 +359,8 @@ class CommAwareRGAT(nn.Module):
                     k = 1
                 zs = outs[k:k + len(rs_src)]
                 for r, o in zip(rs_dst, outs[k + len(rs_src):]):
-                    sds[r] = o + convs[r].project_message.bias
+                    # (fp32 whatever the rows' dtype: the attention kernels read sd as fp32)
+                    sds[r] = o.float() + convs[r].project_message.bias
                 zh = [None] * len(rs_src)
                 xh = None
                 if l == 0 and keep_halo:

@@ -17,6 +17,13 @@ the ``a_src`` term into ``dz``); the halo rows' gradient returns to their owners
 reverse all-to-all-v and is segment-summed there. CPU: the same math in plain PyTorch
 autograd at fp64 (the numerics oracle).
 
+bf16 rows on the GPU (``z``, the halo rows and ``into`` in bf16; ``sd`` / ``a_src`` read as
+fp32): the three kernels of csrc/kernels/gat_bf16.hip, which compute the source score from the
+gathered row itself — no score GEMM and no ``ss`` — and leave dL/da_src as fixed-order partial
+rows; the halo rows and their returning gradient cross the all-to-all-v as bf16. ``remake``
+rebuilds ``z`` with the library GEMM on the same bf16 operands (the rows the forward saw when
+it came from that call; otherwise equal to bf16 rounding). Head passes stay fp32-only.
+
 Reference: experiments/OGB-LSC/RGAT.py:108-206 (per-edge gathers, concat, a linear layer,
 exp without max subtraction, scatter-sum denominator: ~8 passes over E x C memory, and five
 collectives per relation-layer).
@@ -65,7 +72,8 @@ class GatPattern:
         self.nsplit, self.H = int(nsplit), int(n_halo)
         self.R = self.rowptr.numel() - 1
         ncols = self.nsplit + self.H
-        if self.col.numel() and (int(self.col.min()) < 0 or int(self.col.max()) >= ncols):
+        self.col_max = int(self.col.max()) if self.col.numel() else -1
+        if self.col.numel() and (int(self.col.min()) < 0 or self.col_max >= ncols):
             raise ValueError("GatPattern: a column id outside [0, local + halo)")
         from ..parallel.hetero_graph import _transpose_noperm
 
@@ -160,6 +168,108 @@ def _reference(z, zh, sd, a_src, pat: GatPattern):
     return torch.zeros(pat.R, Hh * D, dtype=z.dtype).index_add(0, rows, msg)
 
 
+def _rows16(t: torch.Tensor) -> torch.Tensor:
+    """A bf16 feature array as the bf16 kernels read it: unit column stride, a row stride
+    divisible by 8 and 16-B aligned rows (a column view of a wider GEMM output passes as it
+    is); anything else is copied."""
+    if t.stride(1) == 1 and t.stride(0) % 8 == 0 and t.data_ptr() % 16 == 0:
+        return t
+    return t.contiguous()
+
+
+def _fwd_bf16(ctx, z, zh_static, sd, a_src, into, remake):
+    """bf16 storage (csrc/kernels/gat_bf16.hip): the source scores are computed inside the
+    kernels from the gathered rows — no score GEMM, no ``ss``; halo rows cross the
+    all-to-all-v as bf16."""
+    pat, sg, Hh = ctx.pat, ctx.sg, ctx.heads
+    if into.dtype != torch.bfloat16 or into.shape[0] < pat.R:
+        raise ValueError("gat_relation_into: bf16 rows need a bf16 `into` of the pattern's rows")
+    z = _rows16(z)
+    zh = zh_static
+    if ctx.exchange:
+        zh = sg.a2a(K.gather_rows(z, sg.send_map.idx))
+    if zh is not None:
+        zh = _rows16(zh) if zh.shape[0] else None
+    # the kernels trust the column ids: every one must name a row that is there
+    if zh is None:
+        ok = z.shape[0] > pat.col_max
+    else:
+        ok = z.shape[0] == pat.nsplit and zh.shape[0] == pat.H
+    if not ok or z.shape[0] == 0:
+        raise ValueError("gat_relation_into: the source rows do not match the pattern's "
+                         f"columns ({z.shape[0]} + {0 if zh is None else zh.shape[0]} rows, "
+                         f"{pat.nsplit} + {pat.H} columns)")
+    R = pat.R
+    m = torch.empty(R, Hh, dtype=torch.float32, device=z.device)
+    l = torch.empty_like(m)
+    sdc = sd.detach().float().contiguous()
+    a_flat = a_src.detach().float().reshape(-1).contiguous()
+    _native.ops().gat_fwd_bf16(pat.rowptr, pat.col, z, zh, pat.nsplit, a_flat, sdc, into, 1.0,
+                               m, l, Hh, SLOPE)
+    # remake = (x, W[, xh]): z (and a static zh) are rebuilt in backward by the library GEMM
+    # on the same bf16 operands instead of being kept; an exchanged zh is received again
+    keep_z = z if remake is None else None
+    keep_zh = zh if (remake is None or (zh_static is not None and len(remake) < 3)) else None
+    ctx.zh_remade = keep_zh is None and zh is not None
+    ctx.sd_dtype = sd.dtype
+    ctx.save_for_backward(keep_z, keep_zh, sdc, m, l, a_src)
+    ctx.mark_dirty(into)
+    return into
+
+
+def _bwd_bf16(ctx, g):
+    z, zh, sdc, m, l, a_src = ctx.saved_tensors
+    if ctx.remake is not None:
+        x, W = ctx.remake[0], ctx.remake[1]
+        lin = torch.nn.functional.linear
+        if z is None:
+            z = lin(x, W.to(x.dtype))
+        if ctx.zh_remade:
+            if ctx.exchange:  # every rank rebuilds its z here: the same rows again
+                zh = ctx.sg.a2a(K.gather_rows(z, ctx.sg.send_map.idx))
+            else:
+                zh = lin(ctx.remake[2], W.to(x.dtype))
+    pat, Hh = ctx.pat, ctx.heads
+    ops = _native.ops()
+    g = _rows16(g)
+    R, Ls, C = pat.R, z.shape[0], z.shape[1]
+    dev = g.device
+    c = torch.empty(R, Hh, dtype=torch.float32, device=dev)
+    gsd = torch.empty_like(c)
+    a_flat = a_src.detach().float().reshape(-1).contiguous()
+    ops.gat_bwd_dst_bf16(pat.rowptr, pat.col, z, zh, pat.nsplit, a_flat, sdc, m, l, g, c, gsd,
+                         Hh, SLOPE)
+    # the source side: the local rows, then the halo rows over the tail of the transposed
+    # row pointer; each call leaves its fixed-order partial rows of dL/da_src
+    ga = torch.zeros(C, dtype=torch.float32, device=dev)
+    grads = []
+    for rows, rp in ((z, pat.t_rowptr[:Ls + 1]), (zh, pat.t_rowptr[Ls:])):
+        if rows is None:
+            grads.append(None)
+            continue
+        n = rp.numel() - 1
+        gr = torch.empty(n, C, dtype=torch.bfloat16, device=dev)
+        gss = torch.empty(n, Hh, dtype=torch.float32, device=dev)
+        dap = torch.empty(ops.gat_bf16_da_parts(n, C), C, dtype=torch.float32, device=dev)
+        ops.gat_bwd_src_bf16(rp, pat.t_col, g, rows, a_flat, sdc, m, l, c, gr, gss, dap, Hh,
+                             SLOPE)
+        if dap.shape[0]:
+            ga = ga + ops.col_sum(dap)
+        grads.append(gr)
+    gz, gzh = grads
+    if gz.shape[0] < Ls:  # sources past the pattern's columns have no entries
+        gz = torch.cat([gz, gz.new_zeros(Ls - gz.shape[0], C)])
+    if gzh is not None and ctx.exchange:
+        # the halo rows' gradient back to their owners as bf16, summed there in a fixed order
+        sg = ctx.sg
+        back = sg.a2a_rev(gzh)
+        st = sg.send_map.transpose_csr()
+        K.spmm(st.rowptr, st.col, back, gz, beta=1.0)
+        gzh = None
+    return (gz, gzh if ctx.static else None, gsd.to(ctx.sd_dtype),
+            ga.view(a_src.shape).to(a_src.dtype), g, None, None, None, None)
+
+
 class _GatRelFn(Function):
     @staticmethod
     def forward(ctx, z, zh_static, sd, a_src, into, pat: GatPattern, sg, heads: int,
@@ -169,6 +279,10 @@ class _GatRelFn(Function):
         exchange = zh_static is None and sg is not None and sg.halo is not None
         ctx.pat, ctx.sg, ctx.exchange, ctx.heads = pat, sg, exchange, Hh
         ctx.static = zh_static is not None
+        ctx.bf16 = z.is_cuda and z.dtype == torch.bfloat16
+        if ctx.bf16:
+            ctx.cpu = None
+            return _fwd_bf16(ctx, z, zh_static, sd, a_src, into, remake)
         if not z.is_cuda:
             with torch.enable_grad():
                 zz = z.detach().double().requires_grad_()
@@ -220,6 +334,8 @@ class _GatRelFn(Function):
 
     @staticmethod
     def backward(ctx, g):
+        if ctx.bf16:
+            return _bwd_bf16(ctx, g)
         if ctx.cpu is not None:
             zz, zhh, sdd, aa, out = ctx.cpu
             ins = [t for t in (zz, zhh, sdd, aa) if t is not None]
@@ -310,5 +426,15 @@ def gat_relation_into(z: torch.Tensor, sd: torch.Tensor, a_src: torch.Tensor,
             raise ValueError(f"gat_relation_into: unsupported width {C} / heads {heads}")
     if remake is not None and not z.is_cuda:
         remake = None  # (the CPU oracle keeps its own fp64 graph)
+    if z.is_cuda and z.dtype == torch.bfloat16:
+        # bf16 rows (csrc/kernels/gat_bf16.hip): z, the halo rows and `into` are bf16, sd and
+        # a_src any float dtype (read as fp32; their gradients come back in their own)
+        C = z.shape[1]
+        if C not in (64, 128, 256) or heads not in (1, 2, 4, 8):
+            raise ValueError(f"gat_relation_into: unsupported width {C} / heads {heads}")
+        if HEAD_PASSES:
+            raise ValueError("gat_relation_into: DGRAPH_GAT_HEAD_PASSES is fp32-only")
+        return _GatRelFn.apply(z, zh_static, sd, a_src.contiguous(), into, pat, sg,
+                               int(heads), remake)
     return _GatRelFn.apply(z.contiguous(), zh_static, sd, a_src.contiguous(), into, pat, sg,
                            int(heads), remake)
