@@ -59,12 +59,16 @@ __device__ __forceinline__ const float4* vec(const float* p) {
   return reinterpret_cast<const float4*>(p);
 }
 
-// ---- bf16 storage (gat_bf16.hip): a lane's eight channels are one 16-B vector of bf16,
+// ---- bf16 storage (gat_bf16.hip, dot_attn_bf16.hip): a lane's eight channels are one 16-B vector of bf16,
 // widened to fp32 by a 16-bit shift (exact) and narrowed once, at the store, by
 // round-to-nearest-even (Inf and NaN pass through). LPR = C / 8 there.
 struct f32x8 {
   float4 lo, hi;
 };
+
+__device__ __forceinline__ uint4 load16(const uint16_t* p) {
+  return *reinterpret_cast<const uint4*>(p);
+}
 
 __device__ __forceinline__ f32x8 zero8() {
   f32x8 v;

@@ -105,10 +105,6 @@ struct GatBf16Args {
 
 __device__ __forceinline__ float lrelu(float v, float slope) { return v > 0.f ? v : v * slope; }
 
-__device__ __forceinline__ uint4 load16(const uint16_t* p) {
-  return *reinterpret_cast<const uint4*>(p);
-}
-
 // ss_j[head of this lane] from a gathered row: the ONE definition all three kernels use
 template <int LH>
 __device__ __forceinline__ float score(const f32x8& zv, const f32x8& av) {

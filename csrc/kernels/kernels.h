@@ -636,6 +636,61 @@ hipError_t dot_attn_launch(DotKind kind, DotVariant variant, IType it, int heads
                            const DotAttnArgs& a, hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// The same dot-product attention with bf16 storage (dot_attn_bf16.hip), plain variant only:
+//   e_ij = scale <q_i, k_j> per head; alpha = softmax_j(e_ij); out_i = bf16_rne(sum alpha v_j)
+// * bf16 (raw uint16): q, k, v, k2, v2 (second source: columns >= nsplit; nullable), out,
+//   g = dL/dout, dq, dk, dv. Every one has its own row stride in ELEMENTS (a multiple of 8;
+//   rows 16-B aligned), so k and v may be the column halves of one [N, 2C] buffer.
+// * fp32, contiguous [rows, heads]: stat_m, stat_l (= 1 / sum, 0 for an empty row) and
+//   c_i^h = sum_j alpha_ij <g_i^h, v_j^h>, which dot_attn_bwd_dst_bf16 WRITES (from fp32
+//   quantities, never from the rounded out) and dot_attn_bwd_src_bf16 reads. All arithmetic
+//   is fp32; values are narrowed once, at the store, by round-to-nearest-even.
+// * col is int32. (C, heads): C in 64 / 128 / 256, heads in 1 / 2 / 4 / 8.
+// * fwd / bwd_dst: nrows destination rows; k, v (+ k2, v2) gathered. bwd_src: nrows source
+//   rows with k, v resident; q, g, stat_m, stat_l, c gathered by destination id.
+// * A launch needs row 0 of what it gathers to exist (padding slots read it with weight 0):
+//   of k / v, or of k2 / v2 when nsplit == 0 and they are given; bwd_src: of q, g and the
+//   per-head arrays. The launchers return hipErrorInvalidValue when no such source is given.
+// No beta, no carry-in. No atomics, no LDS, no scratch, fixed summation orders.
+struct DotAttnBf16Args {
+  const int64_t* rowptr;
+  const int32_t* col;
+  int64_t nrows;
+  int C;
+  float scale;
+  const uint16_t* q;   // fwd / bwd_dst: the rows' own q; bwd_src: gathered by destination id
+  int64_t ldq;
+  const uint16_t* k;   // fwd / bwd_dst: gathered (columns < nsplit); bwd_src: the rows' own
+  int64_t ldk;
+  const uint16_t* v;
+  int64_t ldv;
+  const uint16_t* k2;  // second source (columns >= nsplit) or nullptr
+  int64_t ldk2;
+  const uint16_t* v2;
+  int64_t ldv2;
+  int64_t nsplit;
+  uint16_t* out;       // fwd
+  int64_t ldo;
+  float* stat_m;       // [*, heads] written by fwd, read by the backward kernels
+  float* stat_l;
+  const uint16_t* g;   // dL/dout: bwd_dst the rows' own, bwd_src gathered
+  int64_t ldg;
+  float* c;            // [*, heads] written by bwd_dst, read by bwd_src
+  uint16_t* dq;        // bwd_dst
+  int64_t lddq;
+  uint16_t* dk;        // bwd_src
+  int64_t lddk;
+  uint16_t* dv;
+  int64_t lddv;
+};
+
+bool dot_attn_bf16_shape_ok(int C, int heads);
+// nrows <= 0 launches nothing
+hipError_t dot_attn_fwd_bf16(const DotAttnBf16Args& a, int heads, hipStream_t st);
+hipError_t dot_attn_bwd_dst_bf16(const DotAttnBf16Args& a, int heads, hipStream_t st);
+hipError_t dot_attn_bwd_src_bf16(const DotAttnBf16Args& a, int heads, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // Fused fp32 GATv2 graph attention of one relation (gatv2_f32.hip):
 // e_ij = <a, LeakyReLU(xd_i + xs_j)> per head, softmax over each destination row's edges, the
 // weighted gather of xs_j, and the exact adjoint (destination side: dxd and the partial rows

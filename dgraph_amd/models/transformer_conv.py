@@ -16,7 +16,12 @@ MI355X formulation (with a :class:`~dgraph_amd.data.hetero.RelationGraph`):
   backward), issued on every rank whether or not it receives rows; the received rows are
   read as a second source, never concatenated with the local ones;
 * the attention itself is :func:`~dgraph_amd.ops.dot_attn.dot_attention`: three fused
-  kernels, no per-edge tensor (GPU fp32), or its fp64 plain-PyTorch evaluation (CPU);
+  kernels, no per-edge tensor (GPU fp32 or bf16), or its fp64 plain-PyTorch evaluation (CPU);
+* bf16 needs no argument: a module cast with ``.bfloat16()``, or fp32 parameters under
+  ``torch.autocast``, hands bf16 ``q`` and ``[k | v]`` rows to the bf16-storage kernels
+  (csrc/kernels/dot_attn_bf16.hip: fp32 arithmetic, half the gathered bytes), and the
+  synchronous halo exchange then carries bf16 ``[k | v]`` rows, half the message.
+  ``overlap=True``, ``edge_dim`` and ``dropout`` in training raise in bf16, through the op;
 * ``overlap=True`` (more than one rank) moves the exchange inside the attention op
   (:func:`~dgraph_amd.ops.dot_attn.dot_attention_halo`): the interior edges are attended
   over while the ``[k | v]`` rows are on the links and the halo edges are folded into the
@@ -44,8 +49,8 @@ Out of scope here: the same overlap for the GAT and GATv2 layers (their kernels 
 forward yet); edge features together with ``overlap=True`` (the carry-in forward and the
 parts / halo ops take none), in the GAT / GATv2 layers, or projected from ``edge_dim``
 columns inside the kernel (which would avoid the ``[E, C]`` tensor); wiring the layer into
-``CommAwareRGAT``, the lean ``HeteroGraph`` path, GraphCast or the OGB-LSC trainer; bf16;
-PyG's ``beta`` gate between the skip and the attention output; attention dropout together
+``CommAwareRGAT``, the lean ``HeteroGraph`` path, GraphCast or the OGB-LSC trainer; bf16 with
+edge features, dropout or the overlapped exchange; PyG's ``beta`` gate between the skip and the attention output; attention dropout together
 with ``overlap=True`` or ``edge_dim`` (the carry-in forward, the parts / halo ops and the
 edge-feature kernels take none) or in the GAT / GATv2 layers; a fused feature-dropout epilogue.
 """
@@ -147,8 +152,9 @@ class CommAwareTransformerConv(nn.Module):
                 out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads,
                                     dropout_p=self.dropout,
                                     dropout_seed=self._dropout_seed(q.device, dropout_seed))
-            elif edge is None:
-                out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads)
+            elif edge is None:  # (the only call bf16 rows can take: the others raise, in the op)
+                out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads,
+                                    allow_bf16=True)
             else:
                 out = dot_attention(q, kv[:, :C], kv[:, C:], pat, kh, vh, heads=self.heads,
                                     edge=edge)

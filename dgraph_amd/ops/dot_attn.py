@@ -1,4 +1,5 @@
-"""Fused fp32 scaled dot-product graph attention with its exact adjoint (TransformerConv).
+"""Fused scaled dot-product graph attention (fp32, or bf16 storage with fp32 arithmetic) with
+its exact adjoint (TransformerConv).
 
 For one relation (destination rows i, source columns j over ``[local sources | halo rows]``)
 and per head h (channels ``[hD, (h+1)D)`` of ``C = heads * D``)::
@@ -18,6 +19,16 @@ transposed pattern (``dk``, ``dv``; once for the local rows, once for the halo r
 backward's ``c_i = <g_i, out_i>`` per head is one elementwise pass over the saved output.
 Anything else on the GPU raises ``ValueError``. CPU: the same math in plain PyTorch
 autograd at fp64 (the numerics oracle), returned in the input dtype.
+
+GPU, bf16 (``dot_attention(..., allow_bf16=True)`` with ``q``, ``k``, ``v`` and ``kh`` / ``vh``
+all bf16, the same widths and heads; ``CommAwareTransformerConv`` passes the flag): the three
+kernels of csrc/kernels/dot_attn_bf16.hip. Storage is bf16 — eight channels per 16-B
+load, so a gathered ``[k | v]`` row is half the bytes — and every sum is fp32; the output and
+every gradient are bf16, rounded once. The backward's ``c`` is NOT taken from the (rounded)
+output: the destination-side kernel accumulates it in fp32 from the edges and hands it to the
+source side, so the output is not saved. bf16 takes no ``edge=``, no ``dropout_p`` and is not
+available in :func:`dot_attention_parts` / :func:`dot_attention_halo` (a carried accumulator
+would round-trip through bf16); mixed dtypes raise.
 
 With ``edge=`` (``[E, C]``, one row per CSR slot, added to the edge's key and value) the op
 runs the edge variant of the three kernels (csrc/kernels/dot_attn_edge_f32.hip) instead: the
@@ -55,7 +66,8 @@ from torch.autograd import Function
 from .. import _native
 from .gat import GatPattern
 
-SUPPORTED = "float32, C in (64, 128, 256), heads in (1, 2, 4, 8) with C / heads >= 8"
+SUPPORTED = ("float32, or bfloat16 for every operand of dot_attention(allow_bf16=True) without "
+             "edge= and dropout_p; C in (64, 128, 256), heads in (1, 2, 4, 8) with C / heads >= 8")
 
 
 def shape_ok(C: int, heads: int) -> bool:
@@ -92,11 +104,13 @@ def _reference(q, k, v, kh, vh, pat: GatPattern, heads: int, scale: float, edge=
 
 
 def _rows(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
-    """``t`` as the kernels can read it (unit column stride, 16-B aligned rows) — itself when
-    it already is, e.g. a column half of a [N, 2C] buffer."""
+    """``t`` as the kernels can read it (unit column stride, 16-B aligned rows: a row stride
+    that is a multiple of 4 fp32 or 8 bf16 elements) — itself when it already is, e.g. a
+    column half of a [N, 2C] buffer."""
     if t is None:
         return None
-    if t.shape[0] == 0 or (t.stride(1) == 1 and t.stride(0) % 4 == 0 and
+    per16 = 16 // t.element_size()
+    if t.shape[0] == 0 or (t.stride(1) == 1 and t.stride(0) % per16 == 0 and
                            t.stride(0) >= t.shape[1] and t.data_ptr() % 16 == 0):
         return t
     return t.contiguous()
@@ -118,8 +132,8 @@ def _src_side(pat: GatPattern, k, v, kh, vh, bwd_src):
 
     def side(t_rowptr, ks, vs, ncol):
         alloc = torch.empty if ks.shape[0] == ncol else torch.zeros
-        dks = alloc(ks.shape[0], C, dtype=torch.float32, device=ks.device)
-        dvs = alloc(ks.shape[0], C, dtype=torch.float32, device=ks.device)
+        dks = alloc(ks.shape[0], C, dtype=ks.dtype, device=ks.device)
+        dvs = alloc(ks.shape[0], C, dtype=ks.dtype, device=ks.device)
         bwd_src(t_rowptr, ks, vs, dks, dvs)
         return dks, dvs
 
@@ -158,6 +172,41 @@ class _DotAttnFn(Function):
         dk, dv, dkh, dvh = _src_side(pat, k, v, kh, vh, lambda rp, ks, vs, dks, dvs:
                                      ops.dot_attn_bwd_src_f32(rp, pat.t_col, q, g, ks, vs, m, l,
                                                               c, dks, dvs, Hh, scale))
+        return dq, dk, dv, dkh, dvh, None, None, None
+
+
+class _DotAttnBf16Fn(Function):
+    """The attention on bf16 rows (dot_attn_bf16.hip). ``out`` is not saved: the destination
+    side of the backward runs first and accumulates ``c`` in fp32 from the edges, for itself
+    and for the source side."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, kh, vh, pat: GatPattern, heads: int, scale: float):
+        ops = _native.ops()
+        q, k, v, kh, vh = (_rows(t) for t in (q, k, v, kh, vh))
+        R, C = pat.R, q.shape[1]
+        out = torch.empty(R, C, dtype=torch.bfloat16, device=q.device)
+        m = torch.empty(R, heads, dtype=torch.float32, device=q.device)
+        l = torch.empty_like(m)
+        ops.dot_attn_fwd_bf16(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, out, m, l,
+                              heads, scale)
+        ctx.pat, ctx.heads, ctx.scale = pat, heads, scale
+        ctx.save_for_backward(q, k, v, kh, vh, m, l)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        q, k, v, kh, vh, m, l = ctx.saved_tensors
+        pat, Hh, scale = ctx.pat, ctx.heads, ctx.scale
+        ops = _native.ops()
+        g = _rows(g)
+        c = torch.empty_like(m)
+        dq = torch.empty_like(q, memory_format=torch.contiguous_format)
+        ops.dot_attn_bwd_dst_bf16(pat.rowptr, pat.col, q, k, v, kh, vh, pat.nsplit, m, l, g, c,
+                                  dq, Hh, scale)
+        dk, dv, dkh, dvh = _src_side(pat, k, v, kh, vh, lambda rp, ks, vs, dks, dvs:
+                                     ops.dot_attn_bwd_src_bf16(rp, pat.t_col, q, g, ks, vs, m, l,
+                                                               c, dks, dvs, Hh, scale))
         return dq, dk, dv, dkh, dvh, None, None, None
 
 
@@ -241,7 +290,8 @@ def dot_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pat: GatPat
                   kh: Optional[torch.Tensor] = None, vh: Optional[torch.Tensor] = None,
                   scale: Optional[float] = None, *, heads: int = 1,
                   edge: Optional[torch.Tensor] = None, dropout_p: float = 0.0,
-                  dropout_seed: Optional[torch.Tensor] = None) -> torch.Tensor:
+                  dropout_seed: Optional[torch.Tensor] = None,
+                  allow_bf16: bool = False) -> torch.Tensor:
     """``out[R, C]`` of the scaled dot-product attention of ``q [R, C]`` over ``pat``
     (autograd). Columns below ``pat.nsplit`` read ``k`` / ``v``, the others row
     ``column - pat.nsplit`` of ``kh`` / ``vh`` (without them: ``k`` / ``v`` hold every
@@ -256,7 +306,11 @@ def dot_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pat: GatPat
     (the module docstring). ``dropout_seed``: a 1-element int64 tensor on ``q``'s device that
     fixes the mask; ``None`` draws one from the device's torch generator (reproducible under
     ``torch.manual_seed``, no host sync). ``dropout_p = 0`` (the default) is exactly the call
-    without the two arguments; the seed is then ignored. Not available with ``edge=``."""
+    without the two arguments; the seed is then ignored. Not available with ``edge=``.
+
+    ``allow_bf16=True``: operands that are all bf16 run on the bf16-storage kernels (the
+    module docstring). The default keeps the op's earlier contract, under which a caller that
+    handed it down-cast rows by accident got a ``ValueError`` rather than bf16 results."""
     heads = int(heads)
     dropout_p = float(dropout_p)
     if not 0.0 <= dropout_p < 1.0:
@@ -307,9 +361,15 @@ def dot_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, pat: GatPat
             return _reference(up(q), up(k), up(v), up(kh), up(vh), pat, heads, scale).to(dt)
         return _reference(up(q), up(k), up(v), up(kh), up(vh), pat, heads, scale,
                           up(edge)).to(dt)
-    if any(t is not None and t.dtype != torch.float32 for t in (q, k, v, kh, vh)) or \
-            not shape_ok(C, heads):
-        raise ValueError(f"dot_attention: unsupported on the GPU: dtype {q.dtype}, C = {C}, "
+    dtypes = {t.dtype for t in (q, k, v, kh, vh) if t is not None}
+    if allow_bf16 and dtypes == {torch.bfloat16} and shape_ok(C, heads):
+        if edge is not None or dropout_p > 0.0:
+            raise ValueError("dot_attention: unsupported on the GPU: bfloat16 together with "
+                             f"edge= or dropout_p > 0 (supported: {SUPPORTED})")
+        return _DotAttnBf16Fn.apply(q, k, v, kh, vh, pat, heads, scale)
+    if dtypes != {torch.float32} or not shape_ok(C, heads):
+        raise ValueError(f"dot_attention: unsupported on the GPU: dtype "
+                         f"{', '.join(sorted(str(d) for d in dtypes))}, C = {C}, "
                          f"heads = {heads} (supported: {SUPPORTED})")
     if dropout_p > 0.0:
         return _DotAttnDropFn.apply(q, k, v, kh, vh, dropout_seed.reshape(1), pat, heads,
