@@ -1,7 +1,6 @@
 // dgraph_amd — argument checkers shared by the bindings of the fused attention kernels
 // (bindings_gat.cpp, bindings_gat_bf16.cpp, bindings_gatv2.cpp, bindings_dot_attn.cpp,
-// bindings_dot_attn_bf16.cpp). `op`
-// is the op family's name, the prefix of every message ("gatv2", "dot_attn_edge", ...).
+// bindings_dot_attn_bf16.cpp, bindings_gatv2_bf16.cpp). `op` is the op family's name, the prefix of every message ("gatv2", "dot_attn_edge", ...).
 #pragma once
 
 #include <ATen/ATen.h>

@@ -723,6 +723,63 @@ hipError_t gatv2_bwd_src_f32(IType it, const int64_t* rowptr, const void* col, i
                              hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// The same GATv2 attention with bf16 storage (gatv2_bf16.hip):
+//   e_ij = <a, LeakyReLU(xd_i + xs_j)> per head; alpha = softmax_j(e_ij);
+//   out_i = bf16_rne(sum_j alpha_ij xs_j)
+// * bf16 (raw uint16): xd, xs, xs2 (second source: columns >= nsplit; nullable), out,
+//   g = dL/dout, dxd, dxs. Every one has its own row stride in ELEMENTS (a multiple of 8; rows
+//   16-B aligned), so xd and xs may be the column halves of one [N, 2C] buffer.
+// * fp32: att ([C], contiguous, 16-B aligned); stat_m, stat_l (= 1 / sum, 0 for an empty row)
+//   and c_i^h = sum_j alpha_ij <g_i^h, xs_j^h>, [rows, heads] with the shared row stride lds.
+//   gatv2_bwd_dst_bf16 WRITES c (from fp32 quantities, never from the rounded out) and
+//   gatv2_bwd_src_bf16 reads it. All arithmetic is fp32; values are narrowed once, at the
+//   store, by round-to-nearest-even.
+// * col is int32. (C, heads): C in 64 / 128 / 256, heads in 1 / 2 / 4 / 8.
+// * fwd / bwd_dst: nrows destination rows; xs (+ xs2) gathered. bwd_src: nrows source rows
+//   with xs resident; xd, g, stat_m, stat_l, c gathered by destination id.
+// * gatv2_bwd_dst_bf16 also writes da_part [P, C], P = gatv2_bf16_da_parts(nrows, C) (a
+//   function of (nrows, C) only; every row is written): its sum over the rows is dL/datt.
+// * A launch needs row 0 of what it gathers to exist (padding slots read it with weight 0):
+//   of xs, or of xs2 when nsplit == 0 and it is given; bwd_src: of xd, g and the per-head
+//   arrays. The launchers return hipErrorInvalidValue when no such source is given.
+// No beta. No atomics, no scratch, fixed summation orders: two calls give equal bits.
+struct GatV2Bf16Args {
+  const int64_t* rowptr;
+  const int32_t* col;
+  int64_t nrows;
+  int C;
+  float slope;
+  int64_t lds;          // row stride (floats) of stat_m / stat_l / c
+  const float* att;     // [C]
+  const uint16_t* xd;   // l: fwd / bwd_dst the rows' own; bwd_src gathered by destination id
+  int64_t ldxd;
+  const uint16_t* xs;   // r: fwd / bwd_dst gathered (columns < nsplit); bwd_src the rows' own
+  int64_t ldxs;
+  const uint16_t* xs2;  // second source (columns >= nsplit) or nullptr
+  int64_t ldxs2;
+  int64_t nsplit;
+  uint16_t* out;        // fwd
+  int64_t ldo;
+  float* stat_m;        // [*, heads] written by fwd, read by the backward kernels
+  float* stat_l;
+  const uint16_t* g;    // dL/dout: bwd_dst the rows' own, bwd_src gathered
+  int64_t ldg;
+  float* c;             // [*, heads] written by bwd_dst, read by bwd_src
+  uint16_t* dxd;        // bwd_dst
+  int64_t lddxd;
+  float* da_part;       // bwd_dst: [gatv2_bf16_da_parts(nrows, C), C]
+  uint16_t* dxs;        // bwd_src
+  int64_t lddxs;
+};
+
+bool gatv2_bf16_shape_ok(int C, int heads);
+int64_t gatv2_bf16_da_parts(int64_t nrows, int C);
+// nrows <= 0 launches nothing
+hipError_t gatv2_fwd_bf16(const GatV2Bf16Args& a, int heads, hipStream_t st);
+hipError_t gatv2_bwd_dst_bf16(const GatV2Bf16Args& a, int heads, hipStream_t st);
+hipError_t gatv2_bwd_src_bf16(const GatV2Bf16Args& a, int heads, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // Per-edge dot products over a CSR pattern (SDDMM, sddmm.hip):
 //   s[k, h] = scale * row_scale[r(k)] * sum_{d < F / heads} a[r(k), h D + d] * b[col[k], h D + d]
 // for every slot k of the CSR, r(k) the row that holds it. a / b: fp32 or bf16 (dt), row

@@ -22,10 +22,15 @@ MI355X formulation (with a :class:`~dgraph_amd.data.hetero.RelationGraph`):
   in backward), issued on every rank whether or not it receives rows; the received rows are
   read as a second source, never concatenated with the local ones;
 * the attention itself is :func:`~dgraph_amd.ops.gatv2.gatv2_attention`: three fused kernels,
-  no per-edge tensor (GPU fp32), or its fp64 plain-PyTorch evaluation (CPU).
+  no per-edge tensor (GPU fp32 or bf16), or its fp64 plain-PyTorch evaluation (CPU);
+* bf16 needs no argument: a module cast with ``.bfloat16()``, or fp32 parameters under
+  ``torch.autocast``, hands bf16 ``l`` and ``r`` rows to the bf16-storage kernels
+  (csrc/kernels/gatv2_bf16.hip: fp32 arithmetic, half the gathered bytes; ``att`` is widened
+  to fp32 for them), the halo exchange then carries bf16 ``r`` rows, half the message, and
+  the layer returns bf16.
 
 Out of scope here: wiring the layer into ``CommAwareRGAT``, the lean ``HeteroGraph`` path or
-the OGB-LSC trainer; bf16; edge features; attention dropout; averaging the heads instead of
+the OGB-LSC trainer; edge features; attention dropout; averaging the heads instead of
 concatenating them; adding self loops (the caller's graph decides).
 """
 from __future__ import annotations
@@ -96,9 +101,10 @@ class CommAwareGATv2Conv(nn.Module):
                 self._halo = HaloExchange(self.comm)
             xsh = self._halo(xs, graph.pattern)
         out = gatv2_attention(xd, xs, self.att, self._pattern(graph), xsh, heads=self.heads,
-                              negative_slope=self.negative_slope)
+                              negative_slope=self.negative_slope, allow_bf16=True)
         if self.res_net is not None:
             out = out + self.res_net(x)
         if self.bias is not None:
-            out = out + self.bias
+            # (under autocast the rows are bf16 and the parameter fp32: the sum stays bf16)
+            out = out + self.bias.to(out.dtype)
         return out

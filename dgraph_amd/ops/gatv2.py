@@ -1,5 +1,5 @@
-"""Fused fp32 GATv2 graph attention with its exact adjoint (GATv2Conv; Brody et al., "How
-attentive are graph attention networks?").
+"""Fused GATv2 graph attention (fp32, or bf16 storage with fp32 arithmetic) with its exact
+adjoint (GATv2Conv; Brody et al., "How attentive are graph attention networks?").
 
 For one relation (destination rows i, source columns j over ``[local sources | halo rows]``)
 and per head h (channels ``[hD, (h+1)D)`` of ``C = heads * D``)::
@@ -23,6 +23,15 @@ once for the local rows, once for the halo rows). The backward's ``c_i = <g_i, o
 head is one elementwise pass over the saved output. Anything else on the GPU raises
 ``ValueError``. CPU: the same math in plain PyTorch autograd at fp64 (the numerics oracle),
 returned in the input dtype.
+
+GPU, bf16 (``gatv2_attention(..., allow_bf16=True)`` with ``xd``, ``xs`` and ``xsh`` all bf16,
+``att`` fp32 or bf16, the same widths and heads; ``CommAwareGATv2Conv`` passes the flag): the
+three kernels of csrc/kernels/gatv2_bf16.hip. Storage is bf16 — eight channels per 16-B load,
+so every gathered row is half the bytes — and every sum is fp32; the output and the feature
+gradients are bf16, rounded once, ``datt`` comes back in ``att``'s dtype. The backward's ``c``
+is NOT taken from the (rounded) output: the destination-side kernel accumulates it in fp32
+from the edges, in the same single pass that gives ``dxd`` and ``datt``, and hands it to the
+source side, so the output is not saved. Mixed feature dtypes raise.
 """
 from __future__ import annotations
 
@@ -36,7 +45,8 @@ from .. import _native
 from .dot_attn import _rows, shape_ok
 from .gat import GatPattern
 
-SUPPORTED = "float32, C in (64, 128, 256), heads in (1, 2, 4, 8) with C / heads >= 8"
+SUPPORTED = ("float32, or bfloat16 for xd, xs and xsh of gatv2_attention(allow_bf16=True); "
+             "C in (64, 128, 256), heads in (1, 2, 4, 8) with C / heads >= 8")
 
 
 def _reference(xd, xs, xsh, att, pat: GatPattern, heads: int, slope: float):
@@ -110,14 +120,74 @@ class _GATv2Fn(Function):
         return dxd, dxs, dxsh, datt, None, None, None
 
 
+class _GATv2Bf16Fn(Function):
+    """The attention on bf16 rows (gatv2_bf16.hip). ``att`` reaches the kernels as a contiguous
+    fp32 vector. ``out`` is not saved: the destination side of the backward runs first and
+    accumulates ``c`` in fp32 from the edges, for itself and for the source side."""
+
+    @staticmethod
+    def forward(ctx, xd, xs, xsh, att, pat: GatPattern, heads: int, slope: float):
+        ops = _native.ops()
+        xd, xs, xsh = (_rows(t) for t in (xd, xs, xsh))
+        att32 = att.float()
+        if att32.data_ptr() % 16 or not att32.is_contiguous():
+            att32 = att32.contiguous().clone()
+        R, C = pat.R, xd.shape[1]
+        out = torch.empty(R, C, dtype=torch.bfloat16, device=xd.device)
+        m = torch.empty(R, heads, dtype=torch.float32, device=xd.device)
+        l = torch.empty_like(m)
+        ops.gatv2_fwd_bf16(pat.rowptr, pat.col, xd, xs, xsh, pat.nsplit, att32, out, m, l,
+                           heads, slope)
+        ctx.pat, ctx.heads, ctx.slope, ctx.att_dtype = pat, heads, slope, att.dtype
+        ctx.save_for_backward(xd, xs, xsh, att32, m, l)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xd, xs, xsh, att, m, l = ctx.saved_tensors
+        pat, Hh, slope = ctx.pat, ctx.heads, ctx.slope
+        ops = _native.ops()
+        R, C = pat.R, xd.shape[1]
+        g = _rows(g)
+        bf = dict(dtype=torch.bfloat16, device=g.device)
+        c = torch.empty_like(m)
+        dxd = torch.empty(R, C, **bf)
+        # datt leaves the kernel as one partial row per workgroup (fixed partition)
+        P = ops.gatv2_bf16_da_parts(R, C)
+        da_part = torch.empty(P, C, dtype=torch.float32, device=g.device)
+        ops.gatv2_bwd_dst_bf16(pat.rowptr, pat.col, xd, xs, xsh, pat.nsplit, att, m, l, g, c,
+                               dxd, da_part, Hh, slope)
+        datt = ops.col_sum(da_part) if P else torch.zeros(C, dtype=torch.float32,
+                                                          device=g.device)
+        # the source side: the local rows, then the halo rows over the tail of the transposed
+        # row pointer; rows past the pattern's columns have no entries
+        nloc = pat.nsplit if xsh is not None else pat.nsplit + pat.H
+        alloc = torch.empty if xs.shape[0] == nloc else torch.zeros
+        dxs = alloc(xs.shape[0], C, **bf)
+        ops.gatv2_bwd_src_bf16(pat.t_rowptr[:nloc + 1], pat.t_col, xd, g, xs, att, m, l, c, dxs,
+                               Hh, slope)
+        dxsh = None
+        if xsh is not None:
+            alloc = torch.empty if xsh.shape[0] == pat.H else torch.zeros
+            dxsh = alloc(xsh.shape[0], C, **bf)
+            ops.gatv2_bwd_src_bf16(pat.t_rowptr[pat.nsplit:], pat.t_col, xd, g, xsh, att, m, l,
+                                   c, dxsh, Hh, slope)
+        return dxd, dxs, dxsh, datt.to(ctx.att_dtype), None, None, None
+
+
 def gatv2_attention(xd: torch.Tensor, xs: torch.Tensor, att: torch.Tensor, pat: GatPattern,
                     xsh: Optional[torch.Tensor] = None, *, heads: int = 1,
-                    negative_slope: float = 0.2) -> torch.Tensor:
+                    negative_slope: float = 0.2, allow_bf16: bool = False) -> torch.Tensor:
     """``out[R, C]`` of the GATv2 attention of ``xd [R, C]`` over ``pat`` (autograd in ``xd``,
     ``xs``, ``xsh`` and ``att``). Columns below ``pat.nsplit`` read ``xs``, the others row
     ``column - pat.nsplit`` of ``xsh`` (without it: ``xs`` holds every column's row). ``att``
     is ``[C]`` or ``[heads, D]``; ``heads`` is a keyword argument (the tensors stay 2-D, heads
-    are contiguous column blocks)."""
+    are contiguous column blocks).
+
+    ``allow_bf16=True``: ``xd``, ``xs`` and ``xsh`` that are all bf16 (``att`` fp32 or bf16) run
+    on the bf16-storage kernels (the module docstring). The default keeps the op's earlier
+    contract, under which a caller that handed it down-cast rows by accident got a
+    ``ValueError`` rather than bf16 results."""
     heads = int(heads)
     if xd.dim() != 2 or xs.dim() != 2 or xs.shape[1] != xd.shape[1]:
         raise ValueError("gatv2_attention: xd [R, C] and xs [N, C] expected")
@@ -143,6 +213,10 @@ def gatv2_attention(xd: torch.Tensor, xs: torch.Tensor, att: torch.Tensor, pat: 
         dt = xd.dtype
         up = lambda t: None if t is None else t.double()  # noqa: E731
         return _reference(up(xd), up(xs), up(xsh), up(a), pat, heads, slope).to(dt)
+    rows = {t.dtype for t in (xd, xs, xsh) if t is not None}
+    if allow_bf16 and rows == {torch.bfloat16} and shape_ok(C, heads) and \
+            att.dtype in (torch.float32, torch.bfloat16):
+        return _GATv2Bf16Fn.apply(xd, xs, xsh, a, pat, heads, slope)
     if any(t is not None and t.dtype != torch.float32 for t in (xd, xs, xsh, att)) or \
             not shape_ok(C, heads):
         raise ValueError(f"gatv2_attention: unsupported on the GPU: dtype {xd.dtype}, C = {C}, "
