@@ -1,7 +1,8 @@
 // dgraph_amd — dispatcher registration of the fused fp32 GATv2 attention kernels
-// (csrc/kernels/gatv2_f32.hip; ops/gatv2.py). Every shape, dtype, stride and alignment
-// contract the kernels rely on is checked here; column ids are checked against the operand
-// rows once per pattern by the Python caller (ops/gat.py: GatPattern).
+// (csrc/kernels/gatv2_f32.hip and, with edge features, gatv2_edge_f32.hip; ops/gatv2.py).
+// Every shape, dtype, stride and alignment contract the kernels rely on is checked here,
+// before any launch; column ids and transposed slots are checked / built once per pattern
+// by the Python caller (ops/gat.py: GatPattern).
 //
 // Empty sides are legal and never reach a kernel: a relation with no destination rows
 // returns; one whose gathered side has no rows at all (the pattern then has no entries)
@@ -177,6 +178,185 @@ void gatv2_bwd_src_op(const at::Tensor& rowptr, const at::Tensor& col, const at:
                                  cur_stream(xd)));
 }
 
+// ------------------------------------------------------- edge features (gatv2_edge_f32.hip)
+// With edge features a pattern with no entries (col.numel() == 0, so ee / dee / w have no
+// rows) never launches: the empty-row results are plain fills. col is 1-D: ee, dee and w are
+// indexed by its positions.
+constexpr const char* kEdge = "gatv2_edge";
+
+// a per-slot feature array (ee, dee): exactly one row per entry of the pattern
+void edge_rows_f32(const at::Tensor& t, const at::Tensor& ref, int64_t nnz, int64_t cols,
+                   const char* name) {
+  rows_f32(kEdge, t, ref, nnz, cols, name);
+  TORCH_CHECK(t.size(0) == nnz, "gatv2_edge: ", name, " must have one row per entry (", nnz,
+              "), got ", t.sizes());
+}
+
+// the per-slot weights: [nnz, heads] float32 with unit column stride
+void weights(const at::Tensor& w, const at::Tensor& ref, int64_t nnz, int64_t heads) {
+  TORCH_CHECK(w.is_cuda() && w.device() == ref.device() && w.scalar_type() == at::kFloat &&
+                  w.dim() == 2 && w.size(1) == heads && w.size(0) == nnz,
+              "gatv2_edge: w must be float32 [", nnz, ", ", heads, "] on ", ref.device(),
+              ", got ", w.sizes());
+  if (nnz == 0) return;
+  TORCH_CHECK((heads == 1 || w.stride(1) == 1) && w.stride(0) >= heads,
+              "gatv2_edge: w must have unit column stride, got strides ", w.strides());
+}
+
+// what fwd and bwd_dst share: the pattern, xd, the two sources, ee, att
+GatV2EdgeArgs edge_dst_side(const at::Tensor& rowptr, const at::Tensor& col,
+                            const at::Tensor& xd, const at::Tensor& xs,
+                            const c10::optional<at::Tensor>& xs2, int64_t nsplit,
+                            const at::Tensor& ee, const at::Tensor& att,
+                            const at::Tensor& stat_m, int64_t heads, double slope, IType* it,
+                            int64_t* src_rows) {
+  GatV2EdgeArgs a{};
+  a.C = width(xd, heads);
+  *it = pattern(kEdge, rowptr, col, xd, /*col_1d=*/true);
+  a.nrows = rowptr.numel() - 1;
+  a.lds = stat_m.dim() == 2 ? stat_m.stride(0) : 0;
+  rows_f32(kEdge, xd, xd, a.nrows, a.C, "xd");
+  const Sources s = sources(xd, xs, xs2, nsplit, a.C);
+  *src_rows = s.rows;
+  edge_rows_f32(ee, xd, col.numel(), a.C, "ee");
+  a.att = att_vec(att, xd, a.C);
+  a.rowptr = rowptr.data_ptr<int64_t>();
+  a.col = col.data_ptr();
+  a.slope = static_cast<float>(slope);
+  a.xd = xd.data_ptr<float>();
+  a.ldxd = xd.stride(0);
+  a.xs = s.xs;
+  a.ldxs = s.ldxs;
+  a.xs2 = s.xs2;
+  a.ldxs2 = s.ldxs2;
+  a.nsplit = s.nsplit;
+  a.ee = ee.data_ptr<float>();
+  a.ldee = ee.stride(0);
+  return a;
+}
+
+// ee rows = slots
+void gatv2_edge_fwd_op(const at::Tensor& rowptr, const at::Tensor& col, const at::Tensor& xd,
+                       const at::Tensor& xs, const c10::optional<at::Tensor>& xs2,
+                       int64_t nsplit, const at::Tensor& ee, const at::Tensor& att,
+                       at::Tensor& out, double beta, at::Tensor& stat_m, at::Tensor& stat_l,
+                       int64_t heads, double slope) {
+  const c10::DeviceGuard guard(xd.device());
+  IType it;
+  int64_t src_rows;
+  GatV2EdgeArgs a = edge_dst_side(rowptr, col, xd, xs, xs2, nsplit, ee, att, stat_m, heads,
+                                  slope, &it, &src_rows);
+  const int64_t R = a.nrows, nnz = col.numel();
+  rows_f32(kEdge, out, xd, R, a.C, "out");
+  per_head(kEdge, stat_m, xd, R, heads, a.lds, "stat_m");
+  per_head(kEdge, stat_l, xd, R, heads, a.lds, "stat_l");
+  if (R == 0) return;
+  TORCH_CHECK(src_rows > 0 || nnz == 0, "gatv2_edge: entries but no source rows");
+  if (nnz == 0) {  // every row is empty
+    at::Tensor o = out.narrow(0, 0, R);
+    if (beta == 0.0) o.zero_(); else o.mul_(beta);
+    stat_l.narrow(0, 0, R).zero_();
+    return;
+  }
+  a.out = out.data_ptr<float>();
+  a.ldo = out.stride(0);
+  a.beta = static_cast<float>(beta);
+  a.stat_m = stat_m.data_ptr<float>();
+  a.stat_l = stat_l.data_ptr<float>();
+  DG_HIP_CHECK(gatv2_edge_fwd_f32(a, it, static_cast<int>(heads), cur_stream(xd)));
+}
+
+// dee [E, C] and w [E, heads]: every slot written; da_part as gatv2_bwd_dst_f32
+void gatv2_edge_bwd_dst_op(const at::Tensor& rowptr, const at::Tensor& col,
+                           const at::Tensor& xd, const at::Tensor& xs,
+                           const c10::optional<at::Tensor>& xs2, int64_t nsplit,
+                           const at::Tensor& ee, const at::Tensor& att,
+                           const at::Tensor& stat_m, const at::Tensor& stat_l,
+                           const at::Tensor& g, const at::Tensor& c, at::Tensor& dxd,
+                           at::Tensor& dee, at::Tensor& w, at::Tensor& da_part, int64_t heads,
+                           double slope) {
+  const c10::DeviceGuard guard(xd.device());
+  IType it;
+  int64_t src_rows;
+  GatV2EdgeArgs a = edge_dst_side(rowptr, col, xd, xs, xs2, nsplit, ee, att, stat_m, heads,
+                                  slope, &it, &src_rows);
+  const int64_t R = a.nrows, nnz = col.numel();
+  per_head(kEdge, stat_m, xd, R, heads, a.lds, "stat_m");
+  per_head(kEdge, stat_l, xd, R, heads, a.lds, "stat_l");
+  per_head(kEdge, c, xd, R, heads, a.lds, "c");
+  rows_f32(kEdge, g, xd, R, a.C, "g");
+  rows_f32(kEdge, dxd, xd, R, a.C, "dxd");
+  edge_rows_f32(dee, xd, nnz, a.C, "dee");
+  weights(w, xd, nnz, heads);
+  const int64_t P = gatv2_da_parts(R, a.C);
+  TORCH_CHECK(da_part.is_cuda() && da_part.device() == xd.device() &&
+                  da_part.scalar_type() == at::kFloat && da_part.dim() == 2 &&
+                  da_part.size(0) == P && da_part.size(1) == a.C &&
+                  (P == 0 || (da_part.is_contiguous() && al16(da_part.data_ptr()))),
+              "gatv2_edge: da_part must be contiguous, 16-B aligned float32 [", P, ", ", a.C,
+              "] on ", xd.device(), ", got ", da_part.sizes());
+  if (R == 0) return;
+  TORCH_CHECK(src_rows > 0 || nnz == 0, "gatv2_edge: entries but no source rows");
+  if (nnz == 0) {
+    dxd.narrow(0, 0, R).zero_();
+    da_part.zero_();
+    return;
+  }
+  a.stat_m = stat_m.data_ptr<float>();
+  a.stat_l = stat_l.data_ptr<float>();
+  a.g = g.data_ptr<float>();
+  a.ldg = g.stride(0);
+  a.c = c.data_ptr<float>();
+  a.dxd = dxd.data_ptr<float>();
+  a.lddxd = dxd.stride(0);
+  a.dee = dee.data_ptr<float>();
+  a.lddee = dee.stride(0);
+  a.w = w.data_ptr<float>();
+  a.ldw = w.stride(0);
+  a.da_part = da_part.data_ptr<float>();
+  DG_HIP_CHECK(gatv2_edge_bwd_dst_f32(a, it, static_cast<int>(heads), cur_stream(xd)));
+}
+
+// rows = source rows (the transposed pattern; dxs); col = destination rows (g); t_slot = the
+// forward slot (row of dee and w) of each transposed entry
+void gatv2_edge_bwd_src_op(const at::Tensor& rowptr, const at::Tensor& col,
+                           const at::Tensor& t_slot, const at::Tensor& g, const at::Tensor& w,
+                           const at::Tensor& dee, at::Tensor& dxs, int64_t heads) {
+  const c10::DeviceGuard guard(g.device());
+  GatV2EdgeArgs a{};
+  a.C = width(g, heads);
+  const IType it = pattern(kEdge, rowptr, col, g, /*col_1d=*/true);
+  const int64_t R = rowptr.numel() - 1, nnz = col.numel(), nd = g.size(0);
+  TORCH_CHECK(t_slot.is_cuda() && t_slot.device() == g.device() && t_slot.is_contiguous() &&
+                  t_slot.dim() == 1 && t_slot.scalar_type() == col.scalar_type() &&
+                  t_slot.numel() == nnz,
+              "gatv2_edge: t_slot must be contiguous, of col's dtype and length (", nnz,
+              ") on ", g.device());
+  rows_f32(kEdge, g, g, 0, a.C, "g");
+  weights(w, g, nnz, heads);
+  edge_rows_f32(dee, g, nnz, a.C, "dee");
+  rows_f32(kEdge, dxs, g, R, a.C, "dxs");
+  if (R == 0) return;
+  TORCH_CHECK(nd > 0 || nnz == 0, "gatv2_edge: entries but no destination rows");
+  if (nnz == 0) {  // no entries: every source row's gradient is 0
+    dxs.narrow(0, 0, R).zero_();
+    return;
+  }
+  a.rowptr = rowptr.data_ptr<int64_t>();
+  a.col = col.data_ptr();
+  a.t_slot = t_slot.data_ptr();
+  a.nrows = R;
+  a.g = g.data_ptr<float>();
+  a.ldg = g.stride(0);
+  a.w = const_cast<float*>(w.data_ptr<float>());
+  a.ldw = w.stride(0);
+  a.dee = const_cast<float*>(dee.data_ptr<float>());
+  a.lddee = dee.stride(0);
+  a.dxs = dxs.data_ptr<float>();
+  a.lddxs = dxs.stride(0);
+  DG_HIP_CHECK(gatv2_edge_bwd_src_f32(a, it, static_cast<int>(heads), cur_stream(g)));
+}
+
 // rows of da_part for a relation of R destination rows at width C (no device work)
 int64_t gatv2_da_parts_op(int64_t R, int64_t C) {
   TORCH_CHECK(R >= 0 && C > 0 && C <= 256 && C % 4 == 0, "gatv2: bad (R, C) = (", R, ", ", C,
@@ -197,6 +377,15 @@ TORCH_LIBRARY_FRAGMENT(dgraph_amd, m) {
   m.def("gatv2_bwd_src_f32(Tensor rowptr, Tensor col, Tensor xd, Tensor g, Tensor xs, "
         "Tensor att, Tensor stat_m, Tensor stat_l, Tensor c, Tensor(a!) dxs, int heads, "
         "float slope) -> ()");
+  m.def("gatv2_edge_fwd_f32(Tensor rowptr, Tensor col, Tensor xd, Tensor xs, Tensor? xs2, "
+        "int nsplit, Tensor ee, Tensor att, Tensor(a!) out, float beta, Tensor(b!) stat_m, "
+        "Tensor(c!) stat_l, int heads, float slope) -> ()");
+  m.def("gatv2_edge_bwd_dst_f32(Tensor rowptr, Tensor col, Tensor xd, Tensor xs, Tensor? xs2, "
+        "int nsplit, Tensor ee, Tensor att, Tensor stat_m, Tensor stat_l, Tensor g, Tensor c, "
+        "Tensor(a!) dxd, Tensor(b!) dee, Tensor(c!) w, Tensor(d!) da_part, int heads, "
+        "float slope) -> ()");
+  m.def("gatv2_edge_bwd_src_f32(Tensor rowptr, Tensor col, Tensor t_slot, Tensor g, Tensor w, "
+        "Tensor dee, Tensor(a!) dxs, int heads) -> ()");
   m.def("gatv2_da_parts(int R, int C) -> int", &dgraph::gatv2_da_parts_op);
 }
 
@@ -204,4 +393,7 @@ TORCH_LIBRARY_IMPL(dgraph_amd, CUDA, m) {
   m.impl("gatv2_fwd_f32", &dgraph::gatv2_fwd_op);
   m.impl("gatv2_bwd_dst_f32", &dgraph::gatv2_bwd_dst_op);
   m.impl("gatv2_bwd_src_f32", &dgraph::gatv2_bwd_src_op);
+  m.impl("gatv2_edge_fwd_f32", &dgraph::gatv2_edge_fwd_op);
+  m.impl("gatv2_edge_bwd_dst_f32", &dgraph::gatv2_edge_bwd_dst_op);
+  m.impl("gatv2_edge_bwd_src_f32", &dgraph::gatv2_edge_bwd_src_op);
 }

@@ -53,7 +53,7 @@
 // kU = 4 in gatv2_bwd_dst alone it takes 88 .. 97 VGPRs (occupancy 4 .. 5, no scalar
 // register moved) and on an MI355X measures the same within 2 % (PERFORMANCE.md): the depth
 // is not what bounds it, so one kU = 8 stays for all three, as in dot_attn_f32.hip.
-#include "attn_device.h"
+#include "gatv2_device.h"
 #include "kernels.h"
 
 namespace dgraph {
@@ -97,22 +97,7 @@ __device__ __forceinline__ int64_t load_col(const V2Args& a, int64_t pos) {
   return static_cast<int64_t>(static_cast<const IdxT*>(a.col)[pos]);
 }
 
-__device__ __forceinline__ float4 leaky4(const float4& pre, float slope) {
-  return make_float4(pre.x > 0.f ? pre.x : slope * pre.x, pre.y > 0.f ? pre.y : slope * pre.y,
-                     pre.z > 0.f ? pre.z : slope * pre.z, pre.w > 0.f ? pre.w : slope * pre.w);
-}
-
-// a lam per channel (av or its slope multiple; slope at pre == 0)
-__device__ __forceinline__ float4 alam4(const float4& pre, const float4& av, const float4& as) {
-  return make_float4(pre.x > 0.f ? av.x : as.x, pre.y > 0.f ? av.y : as.y,
-                     pre.z > 0.f ? av.z : as.z, pre.w > 0.f ? av.w : as.w);
-}
-
-// this lane's four terms of <a, LeakyReLU(pre)>; one fixed order in all three kernels, so
-// the backward recomputes the forward's scores bitwise
-__device__ __forceinline__ float score4(const float4& av, const float4& pre, float slope) {
-  return dot4(av, leaky4(pre, slope));
-}
+// (leaky4, alam4, score4: gatv2_device.h, shared with gatv2_edge_f32.hip)
 
 // ------------------------------------------------------------------------------------ fwd
 template <typename IdxT, int LPR, int HH>

@@ -723,6 +723,60 @@ hipError_t gatv2_bwd_src_f32(IType it, const int64_t* rowptr, const void* col, i
                              hipStream_t st);
 
 // ---------------------------------------------------------------------------
+// The fp32 GATv2 attention with edge features (gatv2_edge_f32.hip; GATv2Conv with edge_dim):
+//   pre_p = (xd_i + xs_j) + ee_p per CSR slot p (the score only; the message stays xs_j),
+//   e_p = <a, LeakyReLU(pre_p)> per head, softmax over the row's slots.
+// * ee, dee: [E, C] fp32, one row per entry of col in slot order, own row strides; w: [E,
+//   heads] (= alpha_p), row stride ldw. gatv2_edge_bwd_dst writes dee and w, every slot once,
+//   next to dxd and da_part [gatv2_da_parts(nrows, C), C]; gatv2_edge_bwd_src reads them.
+// * gatv2_edge_fwd / gatv2_edge_bwd_dst: nrows destination rows; xs (+ xs2 from nsplit on)
+//   gathered, ee streamed. gatv2_edge_bwd_src: nrows source rows of the transposed pattern
+//   (rowptr with absolute offsets into col = destination ids and t_slot = forward slots, of
+//   col's index type); it gathers g, dee and w only and writes dxs.
+// * (C, heads) as gatv2_f32_shape_ok. A launch needs E > 0 and row 0 of what it gathers
+//   (padding slots read row / slot 0 with weight 0); nrows <= 0 launches nothing.
+struct GatV2EdgeArgs {
+  const int64_t* rowptr;
+  const void* col;
+  const void* t_slot;   // bwd_src
+  int64_t nrows;
+  int C;
+  float slope;
+  int64_t lds;          // row stride (floats) of stat_m / stat_l / c
+  const float* att;     // [C]
+  const float* xd;
+  int64_t ldxd;
+  const float* xs;
+  int64_t ldxs;
+  const float* xs2;     // second source (columns >= nsplit) or nullptr
+  int64_t ldxs2;
+  int64_t nsplit;
+  const float* ee;      // [E, C] by slot
+  int64_t ldee;
+  float* out;           // fwd
+  int64_t ldo;
+  float beta;
+  float* stat_m;        // [*, heads] written by fwd, read by bwd_dst
+  float* stat_l;
+  const float* g;       // dL/dout: bwd_dst the rows' own, bwd_src gathered
+  int64_t ldg;
+  const float* c;       // [*, heads] <g_i^h, out_i^h>
+  float* dxd;           // bwd_dst
+  int64_t lddxd;
+  float* dee;           // [E, C]: written by bwd_dst, read by bwd_src
+  int64_t lddee;
+  float* w;             // [E, heads]: written by bwd_dst, read by bwd_src
+  int64_t ldw;
+  float* da_part;       // bwd_dst
+  float* dxs;           // bwd_src
+  int64_t lddxs;
+};
+
+hipError_t gatv2_edge_fwd_f32(const GatV2EdgeArgs& a, IType it, int heads, hipStream_t st);
+hipError_t gatv2_edge_bwd_dst_f32(const GatV2EdgeArgs& a, IType it, int heads, hipStream_t st);
+hipError_t gatv2_edge_bwd_src_f32(const GatV2EdgeArgs& a, IType it, int heads, hipStream_t st);
+
+// ---------------------------------------------------------------------------
 // The same GATv2 attention with bf16 storage (gatv2_bf16.hip):
 //   e_ij = <a, LeakyReLU(xd_i + xs_j)> per head; alpha = softmax_j(e_ij);
 //   out_i = bf16_rne(sum_j alpha_ij xs_j)

@@ -27,13 +27,23 @@ MI355X formulation (with a :class:`~dgraph_amd.data.hetero.RelationGraph`):
   ``torch.autocast``, hands bf16 ``l`` and ``r`` rows to the bf16-storage kernels
   (csrc/kernels/gatv2_bf16.hip: fp32 arithmetic, half the gathered bytes; ``att`` is widened
   to fp32 for them), the halo exchange then carries bf16 ``r`` rows, half the message, and
-  the layer returns bf16.
+  the layer returns bf16;
+* ``edge_dim=`` (PyG's ``edge_dim``): ``edge_attr [E_local, edge_dim]`` in the relation's CSR
+  slot order (:func:`~dgraph_amd.data.hetero.relation_edge_order` gives that order for a
+  global edge list) is projected by ``lin_edge`` (no bias) to ``[E_local, C]`` and added to
+  ``l_i + r_j`` inside the LeakyReLU: ``e_ij[h] = att[h] . LeakyReLU(l_i[h] + r_j[h] +
+  ee_ij[h])``; the message stays ``r_j`` (``gatv2_attention(..., edge=)``,
+  csrc/kernels/gatv2_edge_f32.hip, fp32). Edge features live with their destination rank, so
+  more than one rank needs no new communication: the halo exchange still carries only ``r``
+  rows.
 
 Out of scope here: wiring the layer into ``CommAwareRGAT``, the lean ``HeteroGraph`` path or
-the OGB-LSC trainer; edge features; attention dropout; averaging the heads instead of
-concatenating them; adding self loops (the caller's graph decides).
+the OGB-LSC trainer; edge features in bf16; attention dropout; averaging the heads instead
+of concatenating them; adding self loops (the caller's graph decides).
 """
 from __future__ import annotations
+
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -47,7 +57,8 @@ from .rgat import _world
 class CommAwareGATv2Conv(nn.Module):
     def __init__(self, in_channels: int, out_channels: int, comm=None, heads: int = 1,
                  negative_slope: float = 0.2, bias: bool = True, residual: bool = False,
-                 share_weights: bool = False, hetero: bool = False):
+                 share_weights: bool = False, hetero: bool = False,
+                 edge_dim: Optional[int] = None):
         super().__init__()
         if out_channels % heads:
             raise ValueError("out_channels must be divisible by heads")
@@ -60,6 +71,9 @@ class CommAwareGATv2Conv(nn.Module):
         self.out_channels = out_channels
         self.lin_src = nn.Linear(in_channels, out_channels)
         self.lin_dst = self.lin_src if share_weights else nn.Linear(in_channels, out_channels)
+        self.edge_dim = edge_dim
+        if edge_dim is not None:  # (no attribute at all otherwise: state_dict keys as before)
+            self.lin_edge = nn.Linear(edge_dim, out_channels, bias=False)
         self.att = nn.Parameter(torch.empty(heads, out_channels // heads))
         nn.init.xavier_uniform_(self.att)  # glorot
         if residual:
@@ -82,8 +96,11 @@ class CommAwareGATv2Conv(nn.Module):
             graph._cache["gatv2_pattern"] = pat
         return pat
 
-    def forward(self, x, graph, x_j=None):
+    def forward(self, x, graph, x_j=None, edge_attr=None):
         C = self.out_channels
+        if (edge_attr is None) != (self.edge_dim is None):
+            raise ValueError("edge_attr is given exactly when the layer has edge_dim")
+        edge = None if edge_attr is None else self.lin_edge(edge_attr)
         xj = x_j if (self.hetero and x_j is not None) else x
         if xj is x and not self.share_weights:
             # one GEMM for both projections: [l | r] = x [W_dst ; W_src]^T + [b_dst | b_src]
@@ -101,7 +118,7 @@ class CommAwareGATv2Conv(nn.Module):
                 self._halo = HaloExchange(self.comm)
             xsh = self._halo(xs, graph.pattern)
         out = gatv2_attention(xd, xs, self.att, self._pattern(graph), xsh, heads=self.heads,
-                              negative_slope=self.negative_slope, allow_bf16=True)
+                              negative_slope=self.negative_slope, allow_bf16=True, edge=edge)
         if self.res_net is not None:
             out = out + self.res_net(x)
         if self.bias is not None:

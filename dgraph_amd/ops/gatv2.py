@@ -32,6 +32,18 @@ gradients are bf16, rounded once, ``datt`` comes back in ``att``'s dtype. The ba
 is NOT taken from the (rounded) output: the destination-side kernel accumulates it in fp32
 from the edges, in the same single pass that gives ``dxd`` and ``datt``, and hands it to the
 source side, so the output is not saved. Mixed feature dtypes raise.
+
+With ``edge=`` (``[E, C]``, one row per CSR slot in the order of ``pat.col``; PyG's
+``GATv2Conv`` with ``edge_dim``) the edge row enters the score only, the message stays
+``xs_j``::
+
+    e_p = sum_{c in head h} att_c * LeakyReLU((xd_i + xs_j) + edge_p)_c
+
+GPU fp32: the three kernels of csrc/kernels/gatv2_edge_f32.hip. The forward and the
+destination side stream the edge rows in slot order; the destination side also writes the
+edge gradient ``dee [E, C]`` and the per-slot weights ``w = alpha [E, heads]``, and the source
+side gathers ``g_i``, ``dee`` and ``w`` through ``GatPattern.t_slot`` instead of recomputing
+any score. The bf16 kernels take no edge term: bf16 rows or a non-fp32 ``edge`` raise.
 """
 from __future__ import annotations
 
@@ -45,12 +57,13 @@ from .. import _native
 from .dot_attn import _rows, shape_ok
 from .gat import GatPattern
 
-SUPPORTED = ("float32, or bfloat16 for xd, xs and xsh of gatv2_attention(allow_bf16=True); "
-             "C in (64, 128, 256), heads in (1, 2, 4, 8) with C / heads >= 8")
+SUPPORTED = ("float32, or bfloat16 for xd, xs and xsh of gatv2_attention(allow_bf16=True) "
+             "without edge=; C in (64, 128, 256), heads in (1, 2, 4, 8) with C / heads >= 8")
 
 
-def _reference(xd, xs, xsh, att, pat: GatPattern, heads: int, slope: float):
-    """The relation's attention output [R, C], differentiable plain PyTorch."""
+def _reference(xd, xs, xsh, att, pat: GatPattern, heads: int, slope: float, edge=None):
+    """The relation's attention output [R, C], differentiable plain PyTorch. ``edge`` [E, C]
+    (one row per slot) is added inside the LeakyReLU."""
     R, C = pat.R, xd.shape[1]
     D = C // heads
     ra = xs if xsh is None else torch.cat([xs[:pat.nsplit], xsh], 0)
@@ -59,7 +72,10 @@ def _reference(xd, xs, xsh, att, pat: GatPattern, heads: int, slope: float):
     rows = torch.repeat_interleave(torch.arange(R, device=xd.device), rowptr[1:] - rowptr[:-1])
     E = rows.numel()
     re = ra[cols]
-    act = F.leaky_relu(xd[rows] + re, slope)  # (its derivative at 0 is ``slope``)
+    pre = xd[rows] + re
+    if edge is not None:
+        pre = pre + edge
+    act = F.leaky_relu(pre, slope)  # (its derivative at 0 is ``slope``)
     e = (act.view(E, heads, D) * att.view(1, heads, D)).sum(-1)
     m = torch.full((R, heads), -float("inf"), dtype=e.dtype, device=xd.device).index_reduce(
         0, rows, e.detach(), "amax", include_self=True)
@@ -120,6 +136,61 @@ class _GATv2Fn(Function):
         return dxd, dxs, dxsh, datt, None, None, None
 
 
+class _GATv2EdgeFn(Function):
+    """The attention with ``edge`` inside the score (gatv2_edge_f32.hip). The destination
+    side of the backward also writes the per-edge gradient and the per-slot weights ``w``,
+    which the source side reads through ``pat.t_slot`` instead of recomputing them."""
+
+    @staticmethod
+    def forward(ctx, xd, xs, xsh, att, edge, pat: GatPattern, heads: int, slope: float):
+        ops = _native.ops()
+        xd, xs, xsh, edge = (_rows(t) for t in (xd, xs, xsh, edge))
+        if att.data_ptr() % 16 or not att.is_contiguous():
+            att = att.contiguous().clone()
+        R, C = pat.R, xd.shape[1]
+        out = torch.empty(R, C, dtype=torch.float32, device=xd.device)
+        m = torch.empty(R, heads, dtype=torch.float32, device=xd.device)
+        l = torch.empty_like(m)
+        ops.gatv2_edge_fwd_f32(pat.rowptr, pat.col, xd, xs, xsh, pat.nsplit, edge, att, out,
+                               0.0, m, l, heads, slope)
+        ctx.pat, ctx.heads, ctx.slope = pat, heads, slope
+        ctx.save_for_backward(xd, xs, xsh, att, edge, out, m, l)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        xd, xs, xsh, att, edge, out, m, l = ctx.saved_tensors
+        pat, Hh, slope = ctx.pat, ctx.heads, ctx.slope
+        ops = _native.ops()
+        R, C = out.shape
+        E = pat.col.numel()
+        g = _rows(g)
+        f32 = dict(dtype=torch.float32, device=g.device)
+        c = (g * out).reshape(R, Hh, C // Hh).sum(-1)
+        dxd = torch.empty_like(out)
+        dee = torch.empty(E, C, **f32)  # every slot has exactly one writer
+        w = torch.empty(E, Hh, **f32)
+        P = ops.gatv2_da_parts(R, C)
+        da_part = torch.empty(P, C, **f32)
+        ops.gatv2_edge_bwd_dst_f32(pat.rowptr, pat.col, xd, xs, xsh, pat.nsplit, edge, att, m,
+                                   l, g, c, dxd, dee, w, da_part, Hh, slope)
+        datt = ops.col_sum(da_part) if P else torch.zeros(C, **f32)
+        # the source side: the local rows, then the halo rows over the tail of the transposed
+        # row pointer; rows past the pattern's columns have no entries
+        nloc = pat.nsplit if xsh is not None else pat.nsplit + pat.H
+        alloc = torch.empty if xs.shape[0] == nloc else torch.zeros
+        dxs = alloc(xs.shape[0], C, **f32)
+        ops.gatv2_edge_bwd_src_f32(pat.t_rowptr[:nloc + 1], pat.t_col, pat.t_slot, g, w, dee,
+                                   dxs, Hh)
+        dxsh = None
+        if xsh is not None:
+            alloc = torch.empty if xsh.shape[0] == pat.H else torch.zeros
+            dxsh = alloc(xsh.shape[0], C, **f32)
+            ops.gatv2_edge_bwd_src_f32(pat.t_rowptr[pat.nsplit:], pat.t_col, pat.t_slot, g, w,
+                                       dee, dxsh, Hh)
+        return dxd, dxs, dxsh, datt, dee, None, None, None
+
+
 class _GATv2Bf16Fn(Function):
     """The attention on bf16 rows (gatv2_bf16.hip). ``att`` reaches the kernels as a contiguous
     fp32 vector. ``out`` is not saved: the destination side of the backward runs first and
@@ -177,7 +248,8 @@ class _GATv2Bf16Fn(Function):
 
 def gatv2_attention(xd: torch.Tensor, xs: torch.Tensor, att: torch.Tensor, pat: GatPattern,
                     xsh: Optional[torch.Tensor] = None, *, heads: int = 1,
-                    negative_slope: float = 0.2, allow_bf16: bool = False) -> torch.Tensor:
+                    negative_slope: float = 0.2, allow_bf16: bool = False,
+                    edge: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``out[R, C]`` of the GATv2 attention of ``xd [R, C]`` over ``pat`` (autograd in ``xd``,
     ``xs``, ``xsh`` and ``att``). Columns below ``pat.nsplit`` read ``xs``, the others row
     ``column - pat.nsplit`` of ``xsh`` (without it: ``xs`` holds every column's row). ``att``
@@ -187,7 +259,12 @@ def gatv2_attention(xd: torch.Tensor, xs: torch.Tensor, att: torch.Tensor, pat: 
     ``allow_bf16=True``: ``xd``, ``xs`` and ``xsh`` that are all bf16 (``att`` fp32 or bf16) run
     on the bf16-storage kernels (the module docstring). The default keeps the op's earlier
     contract, under which a caller that handed it down-cast rows by accident got a
-    ``ValueError`` rather than bf16 results."""
+    ``ValueError`` rather than bf16 results.
+
+    ``edge [E, C]`` (fp32 on the GPU): one row per CSR slot of ``pat`` (the order of
+    ``pat.col``), added to ``xd_i + xs_j`` inside the LeakyReLU (PyG's ``GATv2Conv`` with
+    ``edge_dim``; the message stays ``xs_j``); its gradient is returned like any other.
+    Without it nothing changes. Not available with bf16 rows."""
     heads = int(heads)
     if xd.dim() != 2 or xs.dim() != 2 or xs.shape[1] != xd.shape[1]:
         raise ValueError("gatv2_attention: xd [R, C] and xs [N, C] expected")
@@ -207,12 +284,23 @@ def gatv2_attention(xd: torch.Tensor, xs: torch.Tensor, att: torch.Tensor, pat: 
             xsh.shape[1] != C:
         raise ValueError("gatv2_attention: xs must have pat.nsplit rows and xsh the "
                          "pattern's halo rows")
+    if edge is not None and (edge.dim() != 2 or edge.shape[0] != pat.col.numel() or
+                             edge.shape[1] != C):
+        raise ValueError(f"gatv2_attention: edge must be [{pat.col.numel()}, {C}] (one row per "
+                         f"entry of the pattern), got {tuple(edge.shape)}")
     slope = float(negative_slope)
     a = att.reshape(C)
     if not xd.is_cuda:
         dt = xd.dtype
         up = lambda t: None if t is None else t.double()  # noqa: E731
-        return _reference(up(xd), up(xs), up(xsh), up(a), pat, heads, slope).to(dt)
+        if edge is None:
+            return _reference(up(xd), up(xs), up(xsh), up(a), pat, heads, slope).to(dt)
+        return _reference(up(xd), up(xs), up(xsh), up(a), pat, heads, slope, up(edge)).to(dt)
+    if edge is not None and (edge.dtype != torch.float32 or any(
+            t is not None and t.dtype == torch.bfloat16 for t in (xd, xs, xsh))):
+        raise ValueError(f"gatv2_attention: unsupported on the GPU: edge dtype {edge.dtype} with "
+                         f"{xd.dtype} rows (the edge-feature kernels are fp32; supported: "
+                         f"{SUPPORTED})")
     rows = {t.dtype for t in (xd, xs, xsh) if t is not None}
     if allow_bf16 and rows == {torch.bfloat16} and shape_ok(C, heads) and \
             att.dtype in (torch.float32, torch.bfloat16):
@@ -221,4 +309,6 @@ def gatv2_attention(xd: torch.Tensor, xs: torch.Tensor, att: torch.Tensor, pat: 
             not shape_ok(C, heads):
         raise ValueError(f"gatv2_attention: unsupported on the GPU: dtype {xd.dtype}, C = {C}, "
                          f"heads = {heads} (supported: {SUPPORTED})")
+    if edge is not None:
+        return _GATv2EdgeFn.apply(xd, xs, xsh, a, edge, pat, heads, slope)
     return _GATv2Fn.apply(xd, xs, xsh, a, pat, heads, slope)
