@@ -272,6 +272,25 @@ hipError_t segment_gated_bwd_src(IType it, const int64_t* t_rowptr, const void* 
                                  float* dq, int64_t lddq, float* dv, int64_t lddv,
                                  int64_t nrows, int F, hipStream_t stream);
 
+// The same two passes with bf16 storage (spmm_gated_bf16.hip): k, q, v, g are bf16 (raw
+// uint16), the outputs bf16 or fp32 (out_dt; out and ds share it, and so do dq and dv), all
+// arithmetic fp32, one rounding per stored value. Eight channels per lane and one lane group
+// per row: F % 8 == 0, every row stride a multiple of 8 elements (fp32 outputs: of 4) and
+// every base 16-B aligned, else hipErrorInvalidValue. accumulate needs fp32 outputs (a bf16
+// sum would be rounded twice). A launched kernel gathers row 0 of q / v (of k / g) for the
+// slots past a row's end, so the caller launches only when the pattern has entries.
+hipError_t segment_gated_bf16_fwd(IType it, DType out_dt, const int64_t* rowptr,
+                                  const void* col, const uint16_t* k, int64_t ldk,
+                                  const uint16_t* q, int64_t ldq, const uint16_t* v,
+                                  int64_t ldv, void* out, int64_t ldo, void* ds, int64_t ldds,
+                                  int64_t nrows, int F, bool accumulate, hipStream_t stream);
+hipError_t segment_gated_bf16_bwd_src(IType it, DType out_dt, const int64_t* t_rowptr,
+                                      const void* t_col, const uint16_t* k, int64_t ldk,
+                                      const uint16_t* q, int64_t ldq, const uint16_t* v,
+                                      int64_t ldv, const uint16_t* g, int64_t ldg, void* dq,
+                                      int64_t lddq, void* dv, int64_t lddv, int64_t nrows,
+                                      int F, hipStream_t stream);
+
 // ---------------------------------------------------------------------------
 // Row copy with optional source and destination index (K4/K7/K8 replacement, K-new-1).
 //   out[dst(i)] (+)= x[src(i)]   for i in [0, n)

@@ -40,12 +40,14 @@ def _torch_dirs():
 
 # per-file flags, by file name: gat_bf16.hip, dot_attn_bf16.hip and gatv2_bf16.hip are built
 # without the packed-fp32 VALU forms (their 8-channel axpys are what the compiler would pair
-# up; plain fp32 fmas keep every lane's operation order the one written down)
+# up; plain fp32 fmas keep every lane's operation order the one written down), and so is
+# spmm_gated_bf16.hip (fewer VGPRs in every instantiation: the table in its header)
 _NO_PACKED_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 EXTRA_FLAGS = {
     "gat_bf16.hip": _NO_PACKED_F32,
     "dot_attn_bf16.hip": _NO_PACKED_F32,
     "gatv2_bf16.hip": _NO_PACKED_F32,
+    "spmm_gated_bf16.hip": _NO_PACKED_F32,
 }
 
 

@@ -20,10 +20,13 @@ MI355X formulation:
   the halo exchange carries the ``[q | v]`` send rows as one message under the interior pass;
 * the backward keeps one ``[L, C]`` tensor from the forward pass (``sum_j s (1 - s) v_j``):
   ``dk`` is its elementwise product with the incoming gradient, and ``d[q | v]`` is one gather
-  over the transposed pattern per block, the halo block's rows going home as one message.
+  over the transposed pattern per block, the halo block's rows going home as one message;
+* a layer cast with ``.bfloat16()`` or run under bf16 autocast (``out_channels % 8 == 0``)
+  takes the bf16-storage kernels: bf16 rows gathered, fp32 arithmetic, one rounding per stored
+  value; with a halo block both passes add into fp32 sums that are cast once.
 
 Out of scope here: ``edge_dim`` (edge features in the gate), gate activations other than the
-sigmoid, bf16, and the wiring into the fused executor or ``bench.py``.
+sigmoid, and the wiring into the fused executor or ``bench.py``.
 """
 from __future__ import annotations
 
@@ -69,5 +72,5 @@ class CommAwareResGatedGraphConv(nn.Module):
         if self.lin_skip is not None:
             out = out + self.lin_skip(x)
         if self.bias is not None:
-            out = out + self.bias
+            out = out + self.bias.to(out.dtype)  # (fp32 under autocast: the output stays bf16)
         return out

@@ -118,12 +118,16 @@ def multi_blocks(buf: torch.Tensor, aggregators: tuple, F: int) -> dict:
 def vec_rows(x: torch.Tensor) -> torch.Tensor:
     """``x`` as the fused kernels take a row array: unit column stride, and on the GPU, for
     a width that is a multiple of 4, a row stride divisible by 4 and a 16-B aligned base
-    (a copy only when the view is not)."""
+    (a copy only when the view is not); bf16 rows whose width is a multiple of 8 also need a
+    row stride divisible by 8 (the same 16 bytes: the bf16 gated kernels)."""
     F = x.shape[1]
     if x.stride(1) != 1 and F > 1:
         return x.contiguous()
     if x.is_cuda and F % 4 == 0 and x.shape[0] > 1 and (
             x.stride(0) % 4 or x.data_ptr() % (4 * x.element_size())):
+        return x.contiguous()
+    if x.is_cuda and x.dtype == torch.bfloat16 and F % 8 == 0 and x.shape[0] > 1 and (
+            x.stride(0) % 8 or x.data_ptr() % 16):
         return x.contiguous()
     return x
 
@@ -252,7 +256,7 @@ class _GatedAggregateFn(Function):
     @staticmethod
     def backward(ctx, g):
         k, q, v, ds = ctx.saved_tensors
-        g = vec_rows(g)
+        g = vec_rows(g if g.dtype == k.dtype else g.to(k.dtype))
         dk = g * ds if ctx.needs_input_grad[0] else None
         dq = dv = None
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:

@@ -509,18 +509,27 @@ def segment_softmax_bwd(
     return dx, part
 
 
-def _check_gated_rows(name: str, F: int, ref: torch.Tensor, **arrays) -> None:
-    """The operands of the gated aggregation: 2-D, ``F`` wide, of ``ref``'s dtype (fp32 on
-    the GPU) on its device, unit column stride."""
-    if ref.is_cuda and ref.dtype != torch.float32:
-        raise ValueError(f"{name}: the GPU kernels are float32, got {ref.dtype}")
+def _check_gated_rows(name: str, F: int, ref: torch.Tensor, outputs=(), **arrays) -> None:
+    """The operands of the gated aggregation: 2-D, ``F`` wide, of ``ref``'s dtype (fp32 or
+    bf16 on the GPU; bf16 there needs ``F % 8 == 0``) on its device, unit column stride. The
+    ``outputs`` of a bf16 call may be fp32 instead (all of them: the accumulators of a
+    two-source aggregation, cast once by the caller)."""
+    if ref.is_cuda and ref.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"{name}: the GPU kernels are float32 or bfloat16, got {ref.dtype}")
+    if ref.is_cuda and ref.dtype == torch.bfloat16 and F % 8:
+        raise ValueError(f"{name}: the bfloat16 GPU kernels need a width that is a multiple "
+                         f"of 8, got {F}")
+    outs = [arrays[nm] for nm in outputs if arrays.get(nm) is not None]
+    odt = outs[0].dtype if outs and ref.dtype == torch.bfloat16 and \
+        outs[0].dtype == torch.float32 else ref.dtype
     for nm, a in arrays.items():
         if a is None:
             continue
         if a.dim() != 2 or a.shape[1] != F:
             raise ValueError(f"{name}: {nm} must be [rows, {F}], got {tuple(a.shape)}")
-        if a.dtype != ref.dtype or a.device != ref.device:
-            raise ValueError(f"{name}: {nm} must be {ref.dtype} on {ref.device}, got "
+        want = odt if nm in outputs else ref.dtype
+        if a.dtype != want or a.device != ref.device:
+            raise ValueError(f"{name}: {nm} must be {want} on {ref.device}, got "
                              f"{a.dtype} on {a.device}")
         if F > 1 and a.shape[0] > 0 and a.stride(1) != 1:
             raise ValueError(f"{name}: {nm} must have unit column stride, got strides "
@@ -548,7 +557,11 @@ def segment_gated(
 
     ``accumulate``: ``out`` (and ``ds``) hold the result of an earlier pass over another
     source (the interior block), which this pass adds to; a row without an entry here is left
-    bitwise as it is. Returns ``(out, ds)`` (``ds`` is ``None`` when not asked for)."""
+    bitwise as it is. Returns ``(out, ds)`` (``ds`` is ``None`` when not asked for).
+
+    bf16 rows run the bf16-storage kernels on the GPU (fp32 arithmetic, one rounding per
+    stored value; ``F % 8 == 0``); ``out`` / ``ds`` may then be given as fp32 buffers, and
+    ``accumulate`` needs them so there: a bf16 sum would be rounded twice."""
     R = rowptr.numel() - 1
     F = k.shape[1]
     if accumulate and (out is None or (want_ds and ds is None)):
@@ -557,14 +570,19 @@ def segment_gated(
         out = torch.empty(R, F, dtype=k.dtype, device=k.device)
     if ds is None and want_ds:
         ds = torch.empty(out.shape[0], F, dtype=k.dtype, device=k.device)
-    _check_gated_rows("segment_gated", F, k, k=k, q=q, v=v, out=out, ds=ds)
+    _check_gated_rows("segment_gated", F, k, ("out", "ds"), k=k, q=q, v=v, out=out, ds=ds)
     if q.shape[0] != v.shape[0]:
         raise ValueError("segment_gated: q and v must have the same row count, got "
                          f"{q.shape[0]} and {v.shape[0]}")
     if k.shape[0] < R or out.shape[0] < R or (ds is not None and ds.shape[0] < R):
         raise ValueError(f"segment_gated: k, out and ds need >= {R} rows")
     if _native_ok(k):
-        _native.ops().segment_gated_fwd(rowptr, col, k, q, v, out, ds, bool(accumulate))
+        if accumulate and out.dtype == torch.bfloat16:
+            raise ValueError("segment_gated: accumulate on the GPU needs float32 out / ds for "
+                             "bfloat16 rows (one rounding per value)")
+        ops = _native.ops()
+        fwd = ops.segment_gated_bf16_fwd if k.dtype == torch.bfloat16 else ops.segment_gated_fwd
+        fwd(rowptr, col, k, q, v, out, ds, bool(accumulate))
         return out, ds
     return _ref.segment_gated(rowptr, col, k, q, v, out, ds, accumulate)
 
@@ -584,21 +602,26 @@ def segment_gated_bwd_src(
     destination rows of ``k`` / ``g``) of ANY subset of the entries: per entry ``s =
     sigmoid(k[r] + q[c])``, ``dv[c] = sum s g[r]`` and ``dq[c] = v[c] sum s (1 - s) g[r]``.
     Every source row is written (zeros for one nobody reads). ``dq`` / ``dv`` may be the
-    halves of one ``[C, 2F]`` buffer. No atomics. Returns ``(dq, dv)``."""
+    halves of one ``[C, 2F]`` buffer. No atomics. Returns ``(dq, dv)``. bf16 rows as in
+    :func:`segment_gated`; ``dq`` / ``dv`` may then be fp32 buffers."""
     C = t_rowptr.numel() - 1
     F = q.shape[1]
     if dq is None:
         dq = torch.empty(C, F, dtype=q.dtype, device=q.device)
     if dv is None:
         dv = torch.empty(C, F, dtype=q.dtype, device=q.device)
-    _check_gated_rows("segment_gated_bwd_src", F, q, k=k, q=q, v=v, g=g, dq=dq, dv=dv)
+    _check_gated_rows("segment_gated_bwd_src", F, q, ("dq", "dv"), k=k, q=q, v=v, g=g, dq=dq,
+                      dv=dv)
     if min(q.shape[0], v.shape[0], dq.shape[0], dv.shape[0]) < C:
         raise ValueError(f"segment_gated_bwd_src: q, v, dq and dv need >= {C} rows")
     if k.shape[0] < g.shape[0]:
         raise ValueError("segment_gated_bwd_src: k has fewer rows than g "
                          f"({k.shape[0]} < {g.shape[0]})")
     if _native_ok(q):
-        _native.ops().segment_gated_bwd_src(t_rowptr, t_col, k, q, v, g, dq, dv)
+        ops = _native.ops()
+        bwd = ops.segment_gated_bf16_bwd_src if q.dtype == torch.bfloat16 else \
+            ops.segment_gated_bwd_src
+        bwd(t_rowptr, t_col, k, q, v, g, dq, dv)
         return dq, dv
     return _ref.segment_gated_bwd_src(t_rowptr, t_col, k, q, v, g, dq, dv)
 

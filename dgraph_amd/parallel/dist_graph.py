@@ -778,16 +778,27 @@ class DistGraph:
             raise ValueError(f"aggregate_gated: qv must be [L, {2 * F}] ([q | v]), got "
                              f"{tuple(qv.shape)}")
         it = self.interior
-        out = torch.empty(L, F, dtype=k.dtype, device=k.device)
-        ds = torch.empty(L, F, dtype=k.dtype, device=k.device)
+        # bf16 rows with a halo block: both passes add into fp32 sums, cast once at the end
+        # (a bf16 out accumulated by the second pass would be rounded twice)
+        wide = k.dtype == torch.bfloat16 and self.halo is not None
+        adt = torch.float32 if wide else k.dtype
+        out = torch.empty(L, F, dtype=adt, device=k.device)
+        ds = torch.empty(L, F, dtype=adt, device=k.device)
         saved = dict(ds=ds, halo=None)
+
+        def done():
+            if wide:
+                saved["ds"] = ds.to(k.dtype)
+                return out.to(k.dtype), saved
+            return out, saved
+
         if self.halo is None or halo_rows is not None:
             K.segment_gated(it.rowptr, it.col, k, qv[:, :F], qv[:, F:], out, ds)
             if self.halo is not None:
                 K.segment_gated(self.halo.rowptr, self.halo.col, k, halo_rows[:, :F],
                                 halo_rows[:, F:], out, ds, accumulate=True)
             saved["halo"] = halo_rows
-            return out, saved
+            return done()
         # the exchanges depend on the plan alone (a rank with sends and no halo entry posts
         # them too); a column chunk carries the same channel range of q and of v
         idx = self.send_map.idx
@@ -816,7 +827,7 @@ class DistGraph:
         else:  # back to [q | v]
             saved["halo"] = torch.cat([p[2][:, :p[1] - p[0]] for p in pend] +
                                       [p[2][:, p[1] - p[0]:] for p in pend], 1)
-        return out, saved
+        return done()
 
     def aggregate_gated_T(self, g: torch.Tensor, k: torch.Tensor, qv: torch.Tensor,
                           saved: dict):
@@ -832,8 +843,13 @@ class DistGraph:
         L, F = self.L, k.shape[1]
         it = self.interior if self.interior.symmetric else self.interior.transpose()
         self.edges_aggregated += it.nnz + (self.halo.nnz if self.halo is not None else 0)
+        if g.dtype != k.dtype:  # (an fp32 gradient of a bf16 output, under autocast)
+            g = g.to(k.dtype)
         dk = g * saved["ds"]
-        dqv = torch.empty(L, 2 * F, dtype=k.dtype, device=k.device)
+        # bf16 rows with a halo block: the interior kernel writes fp32 sums, the received rows
+        # (bf16, each rounded once by its sender) are added in fp32, one cast at the end
+        wide = k.dtype == torch.bfloat16 and self.halo is not None
+        dqv = torch.empty(L, 2 * F, dtype=torch.float32 if wide else k.dtype, device=k.device)
         q, v, dq, dv = qv[:, :F], qv[:, F:], dqv[:, :F], dqv[:, F:]
         if self.halo is None:
             K.segment_gated_bwd_src(it.rowptr, it.col, k, q, v, g, dq, dv)
@@ -855,6 +871,8 @@ class DistGraph:
         st = self.send_map.transpose_csr().compact_rows()
         for c0, c1, sg, work in pend:
             work.wait()
+            if wide:
+                sg = sg.float()
             if (c0, c1) == (0, F):  # the message has the layout of dqv
                 K.spmm(st.rowptr, st.col, sg, dqv, beta=1.0, split=_hs(st), row_map=st.row_map)
                 continue
@@ -862,7 +880,7 @@ class DistGraph:
             for src, dst in ((sg[:, :w], dq[:, c0:c1]), (sg[:, w:], dv[:, c0:c1])):
                 K.spmm(st.rowptr, st.col, src, dst, beta=1.0, split=_hs(st),
                        row_map=st.row_map)
-        return dk, dqv
+        return dk, (dqv.to(k.dtype) if wide else dqv)
 
     def _edge_blocks(self, e_int, e_halo, x: torch.Tensor, name: str):
         """The per-slot edge rows of the two blocks, checked: ``e_int`` ``[interior.nnz, F]``
